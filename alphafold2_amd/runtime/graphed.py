@@ -16,7 +16,28 @@ Requirements on the step function:
 
 torch.cuda.CUDAGraph IS hipGraph on ROCm.
 """
+import time
+
 import torch
+
+# the NCCL/RCCL process group's watchdog thread wakes up this often
+_WATCHDOG_PERIOD_S = 0.1
+
+
+def _drain_collective_watchdog():
+    """Let the process group's watchdog retire the warmup collectives.
+
+    The watchdog thread keeps polling the completion event of every
+    eagerly issued collective (hipEventQuery) until it has seen it done.
+    Such a call from another thread while a global-mode stream capture is
+    open invalidates the capture, and the watchdog then takes the process
+    down.  Call with the device idle: every pending event is complete, so
+    the watchdog drops them all at its next wake-up and makes no further
+    HIP call until a collective is issued outside a capture."""
+    dist = torch.distributed
+    if dist.is_available() and dist.is_initialized() \
+            and dist.get_backend() == 'nccl':
+        time.sleep(2.5 * _WATCHDOG_PERIOD_S)
 
 
 class GraphedTrainStep:
@@ -43,6 +64,7 @@ class GraphedTrainStep:
                 step_fn()
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
+        _drain_collective_watchdog()
 
         self.capture_error = None
         try:

@@ -10,6 +10,11 @@ Single process per GPU; for --gpus N the driver launches this under
 torch.distributed.run with one rank per GPU over RCCL.  `value` is the
 whole-job aggregate samples/sec across all ranks (weak scaling: per-GPU
 work fixed as N grows).
+
+A plain run does only what the headline figure needs: set up, warm up,
+time --steps steps, print the JSON result line.  --dump-outputs DIR
+additionally writes the last timed step's outputs as .npy files;
+--full adds the secondary figures (peak HBM).
 """
 import argparse
 import json
@@ -60,7 +65,43 @@ def parse_args():
                         'memory) at a 2-GEMM recompute cost — pushes '
                         'per-GPU batch beyond 6')
     p.add_argument('--device', type=str, default=None)
+    p.add_argument('--dump-outputs', type=str, default=None, metavar='DIR',
+                   help='after the timed steps write what the last timed '
+                        'step returned (loss, distogram logits, coords / '
+                        'angle logits when predicted) as DIR/<name>.npy, '
+                        'float32; inputs are seeded, so two builds can be '
+                        'compared output for output')
+    p.add_argument('--full', action='store_true',
+                   help='also report what the headline figure does not '
+                        'need (peak HBM of the step)')
     return p.parse_args()
+
+
+# --dump-outputs writes at most this many bytes of array data in all
+DUMP_BUDGET_BYTES = 60 * 10**6
+
+
+def dump_outputs(dirname, tensors, budget=DUMP_BUDGET_BYTES):
+    """Write each tensor as dirname/<name>.npy in float32.  The byte
+    budget is shared smallest-first; a tensor larger than its share is
+    written as a 1-D sample of its flattened values at sorted indices
+    drawn without replacement from a generator seeded with 0, so the
+    same shape always yields the same sample."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = sorted(((name, t.detach().float().cpu().numpy())
+                     for name, t in tensors.items()),
+                    key=lambda kv: kv[1].nbytes)
+    left = budget
+    for i, (name, a) in enumerate(arrays):
+        share = left // (len(arrays) - i)
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(
+                a.size, share // a.itemsize, replace=False)
+            idx.sort()
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        left -= a.nbytes
 
 
 def main():
@@ -156,6 +197,21 @@ def main():
                                   ('phi', constants.PHI_BUCKETS),
                                   ('omega', constants.OMEGA_BUCKETS))}
 
+    # --dump-outputs: what the step hands back besides the loss, copied
+    # into buffers of their own that every step overwrites.  Holding on
+    # to the step's own tensors instead would change how the allocator
+    # lays out the step's activations, and on MI355X that changed both
+    # the step time (+3%) and the values of later steps; with the copies
+    # the step allocates exactly what it does without the option.  The
+    # buffers are allocated in the first (eager) step, so a captured
+    # step only records the copies.
+    outputs = {}
+
+    def keep(name, t):
+        if name not in outputs:
+            outputs[name] = torch.empty_like(t)
+        outputs[name].copy_(t.detach())
+
     def step():
         optimizer.zero_grad(set_to_none=not use_graph)
         if use_bf16:
@@ -187,14 +243,33 @@ def main():
                     alog = getattr(ret, f'{name}_logits')
                     loss = loss + 0.1 * torch.nn.functional.cross_entropy(
                         alog.permute(0, 3, 1, 2).float(), tgt)
+        if args.dump_outputs:
+            keep('distance_logits', ret.distance)
+            if want_coords:
+                keep('coords', coords)
+            if args.predict_angles:
+                for name in angle_targets:
+                    keep(f'{name}_logits', getattr(ret, f'{name}_logits'))
         loss.backward()
         engine.finalize()
         optimizer.step()
         return loss
 
-    def sync():
+    def sync(more_steps=False):
         if device.type == 'cuda':
-            torch.cuda.synchronize()
+            if more_steps and use_graph:
+                # Known issue (README): a device or stream synchronize
+                # BETWEEN two replays of the captured step leaves every
+                # later replay with a NaN loss at the flagship config
+                # (measured on MI355X / ROCm 7.0.2; a host sleep, or no
+                # wait at all, does not).  Cause not found, so wait for
+                # the warmup replays by polling an event instead.
+                done = torch.cuda.Event()
+                done.record()
+                while not done.query():
+                    time.sleep(0.001)
+            else:
+                torch.cuda.synchronize()
         if is_dist:
             dist.barrier()
 
@@ -209,17 +284,21 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    sync()
-    if rank == 0 and device.type == 'cuda':
+    sync(more_steps=True)
+    if args.full and rank == 0 and device.type == 'cuda':
         peak = torch.cuda.max_memory_allocated(device) / 2**30
         total = torch.cuda.get_device_properties(device).total_memory / 2**30
         print(f"# peak HBM: {peak:.1f} / {total:.0f} GiB", flush=True)
 
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        loss = step()
     sync()
     elapsed = time.perf_counter() - t0
+
+    # each rank has its own inputs; rank 0's outputs are the ones written
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(outputs, loss=loss))
 
     # max over ranks = whole-job wall time
     if is_dist:
