@@ -271,7 +271,10 @@ def tri_proj_gates(fused, hdim, row_mask=None):
 def softclamp_gate(x, gates, row_mask=None):
     """out = x * sigmoid(gates) (* row_mask broadcast per row).
     row_mask: optional bool with shape == x.shape[:-1]."""
-    if x.shape == gates.shape and using_hip(x, 'gatemul_fwd'):
+    # the kernel reads both operands as x's dtype: a mixed pair (e.g. an
+    # fp32 residual with bf16 gates) takes the eager composition
+    if (x.shape == gates.shape and x.dtype == gates.dtype
+            and using_hip(x, 'gatemul_fwd')):
         from .hip_autograd import hip_gatemul
         return hip_gatemul(x, gates, row_mask)
     out = eager.softclamp_gate(x, gates)

@@ -1423,8 +1423,10 @@ namespace {
 TView make_view(const at::Tensor& t) {
   TORCH_CHECK(t.dim() == 4 && t.size(3) == DH && t.stride(3) == 1,
               "attention tensors must be 4-D (B, h, L, 64), last dim dense");
-  TORCH_CHECK(t.stride(2) % 8 == 0 && t.stride(1) % 8 == 0,
-              "attention tensor strides must be 16-byte aligned");
+  TORCH_CHECK(t.stride(2) % 8 == 0 && t.stride(1) % 8 == 0 &&
+              (t.size(0) == 1 || t.stride(0) % 8 == 0) &&
+              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              "attention tensor base and strides must be 16-byte aligned");
   return TView{reinterpret_cast<const bf16_t*>(t.data_ptr()),
                t.stride(0), t.stride(1), t.stride(2)};
 }
@@ -1432,6 +1434,48 @@ TView make_view(const at::Tensor& t) {
 TViewMut make_view_mut(at::Tensor& t) {
   TView v = make_view(t);
   return TViewMut{const_cast<bf16_t*>(v.p), v.bs, v.hs, v.rs};
+}
+
+// every operand is reinterpreted as bf16 by the launchers: a wider dtype
+// would be misread, a narrower one read past its end
+void check_bf16(const at::Tensor& t, const at::Tensor& q, const char* fn,
+                const char* name) {
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, fn, ": ", name,
+              " must be bf16, got ", t.scalar_type());
+  TORCH_CHECK(t.device() == q.device(), fn, ": ", name,
+              " must be on q's device");
+}
+
+// shapes the kernels index with: q (B / q_repeat, H, Lq, 64),
+// k and v (B, H, Lk, 64), bias (B / bias_repeat, H, Lq, Lk)
+void check_qkv_bias(const at::Tensor& q, const at::Tensor& k,
+                    const at::Tensor& v,
+                    const c10::optional<at::Tensor>& bias,
+                    long bias_repeat, long q_repeat, const char* fn) {
+  check_bf16(q, q, fn, "q");
+  check_bf16(k, q, fn, "k");
+  check_bf16(v, q, fn, "v");
+  TORCH_CHECK(q.dim() == 4 && k.dim() == 4 && v.dim() == 4, fn,
+              ": q, k and v must be 4-D (B, h, L, 64)");
+  TORCH_CHECK(q_repeat >= 1 && bias_repeat >= 1, fn,
+              ": q_repeat and bias_repeat must be >= 1");
+  const long B = k.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
+  TORCH_CHECK(q.size(0) * q_repeat == B, fn,
+              ": q batch must be B / q_repeat");
+  TORCH_CHECK(k.size(1) == H && v.size(0) == B && v.size(1) == H &&
+              v.size(2) == Lk, fn,
+              ": k and v must both be (B, h, Lk, 64) with q's head count");
+  if (bias.has_value()) {
+    check_bf16(*bias, q, fn, "bias");
+    TORCH_CHECK(B % bias_repeat == 0, fn, ": batch ", B,
+                " is not divisible by bias_repeat ", bias_repeat);
+    TORCH_CHECK(bias->dim() == 4 && bias->size(0) == B / bias_repeat &&
+                bias->size(1) == H && bias->size(2) == Lq &&
+                bias->size(3) == Lk, fn,
+                ": bias must be (B / bias_repeat, h, Lq, Lk) = (",
+                B / bias_repeat, ", ", H, ", ", Lq, ", ", Lk, "), got ",
+                bias->sizes());
+  }
 }
 
 }  // namespace
@@ -1442,9 +1486,8 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  long bias_repeat, double scale,
                                  long q_repeat) {
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "attn_fwd: bf16 only");
+  check_qkv_bias(q, k, v, bias, bias_repeat, q_repeat, "attn_fwd");
   const int B = k.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
-  TORCH_CHECK(q.size(0) * q_repeat == B,
-              "q batch must be B / q_repeat");
 
   // out in (B, Lq, H, DH) memory (the layout downstream Linears want),
   // exposed as a (B, H, Lq, DH) strided view
@@ -1496,9 +1539,35 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  c10::optional<at::Tensor> dq_out,
                                  c10::optional<at::Tensor> dk_out,
                                  c10::optional<at::Tensor> dv_out) {
+  check_qkv_bias(q, k, v, bias, bias_repeat, q_repeat, "attn_bwd");
   const int B = k.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
-  TORCH_CHECK(q.size(0) * q_repeat == B,
-              "q batch must be B / q_repeat");
+  check_bf16(dout, q, "attn_bwd", "dout");
+  check_bf16(out, q, "attn_bwd", "out");
+  TORCH_CHECK(dout.dim() == 4 && dout.size(0) == B && dout.size(1) == H &&
+              dout.size(2) == Lq && dout.size(3) == DH &&
+              out.sizes() == dout.sizes(),
+              "attn_bwd: dout and out must be (B, h, Lq, 64)");
+  TORCH_CHECK(lse.scalar_type() == at::kFloat && lse.is_contiguous() &&
+              lse.numel() == (long)B * H * Lq && lse.device() == q.device(),
+              "attn_bwd: lse must be contiguous fp32 (B, h, Lq)");
+  TORCH_CHECK(!need_dbias || bias.has_value(),
+              "attn_bwd: need_dbias requires a bias");
+  TORCH_CHECK(dq_out.has_value() == dk_out.has_value() &&
+              dq_out.has_value() == dv_out.has_value(),
+              "attn_bwd: dq_out, dk_out and dv_out must be given together");
+  if (dq_out.has_value()) {
+    check_bf16(*dq_out, q, "attn_bwd", "dq_out");
+    check_bf16(*dk_out, q, "attn_bwd", "dk_out");
+    check_bf16(*dv_out, q, "attn_bwd", "dv_out");
+    // dq is written per batch entry even under q_repeat (the caller
+    // folds the tie group afterwards)
+    TORCH_CHECK(dq_out->dim() == 4 && dq_out->size(0) == B &&
+                dq_out->size(1) == H && dq_out->size(2) == Lq &&
+                dq_out->size(3) == DH,
+                "attn_bwd: dq_out must be (B, h, Lq, 64)");
+    TORCH_CHECK(dk_out->sizes() == k.sizes() && dv_out->sizes() == v.sizes(),
+                "attn_bwd: dk_out and dv_out must have k's and v's shapes");
+  }
   if (dout.stride(3) != 1) dout = dout.contiguous();
 
   auto delta = at::empty({B, H, Lq}, lse.options());

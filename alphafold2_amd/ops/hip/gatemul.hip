@@ -96,19 +96,57 @@ long gm_grid(long rows, int rpb) {
   return blocks < cap ? blocks : (cap > 0 ? cap : 1);
 }
 
+// operands are reinterpreted as T* by the launch macros: a mismatched
+// dtype or a strided innermost dim would be read past its end
+void gm_check_operand(const at::Tensor& t, const at::Tensor& x,
+                      const char* fn, const char* name) {
+  TORCH_CHECK(t.scalar_type() == x.scalar_type(), fn, ": ", name,
+              " must have x's dtype (", x.scalar_type(), "), got ",
+              t.scalar_type());
+  TORCH_CHECK(t.device() == x.device(), fn, ": ", name,
+              " must be on x's device");
+  TORCH_CHECK(t.sizes() == x.sizes(), fn, ": ", name,
+              " must have x's shape");
+  TORCH_CHECK(t.size(-1) == 1 || t.stride(-1) == 1, fn, ": ", name,
+              " must be dense in its last dim");
+}
+
+bool gm_aligned16(const at::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+const unsigned char* gm_check_rowmask(const c10::optional<at::Tensor>& rm,
+                                      const at::Tensor& x, long rows,
+                                      const char* fn) {
+  if (!rm.has_value()) return nullptr;
+  TORCH_CHECK(rm->scalar_type() == at::kByte, fn,
+              ": rowmask must be uint8, got ", rm->scalar_type());
+  TORCH_CHECK(rm->device() == x.device(), fn,
+              ": rowmask must be on x's device");
+  TORCH_CHECK(rm->numel() == rows && rm->is_contiguous(), fn,
+              ": rowmask must be contiguous with one byte per row (", rows,
+              "), got ", rm->numel());
+  return rm->data_ptr<unsigned char>();
+}
+
 }  // namespace
 
 // x/g: (rows, C) with uniform row strides xs/gs (elements); y contiguous
 at::Tensor gatemul_fwd(at::Tensor x, at::Tensor g, long xs, long gs,
                        c10::optional<at::Tensor> rowmask) {
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0,
+              "gatemul_fwd: x must be non-empty");
+  TORCH_CHECK(x.size(-1) == 1 || x.stride(-1) == 1,
+              "gatemul_fwd: x must be dense in its last dim");
+  gm_check_operand(g, x, "gatemul_fwd", "g");
   const int C = x.size(-1);
   const long rows = x.numel() / C;
+  const bool rm = rowmask.has_value();
+  const unsigned char* rm_ptr =
+      gm_check_rowmask(rowmask, x, rows, "gatemul_fwd");
   auto y = at::empty(x.sizes(), x.options());
   const int block = 256;
   auto stream = at::cuda::getCurrentHIPStream();
-  const bool rm = rowmask.has_value();
-  const unsigned char* rm_ptr =
-      rm ? rowmask->data_ptr<unsigned char>() : nullptr;
 
 #define LAUNCH_G2(T, VEC, GROUP, RM)                                        \
   hipLaunchKernelGGL((gatemul_fwd_kernel<T, VEC, GROUP, RM>),               \
@@ -129,8 +167,11 @@ at::Tensor gatemul_fwd(at::Tensor x, at::Tensor g, long xs, long gs,
     else LAUNCH_G(T, VEC, 64);                                              \
   } while (0)
 
-  const bool al8 = (C % 8) == 0 && (xs % 8) == 0 && (gs % 8) == 0;
-  const bool al4 = (C % 4) == 0 && (xs % 4) == 0 && (gs % 4) == 0;
+  // the vector paths move 16 bytes per access: row strides AND base
+  // pointers (a slice can start mid-vector) must keep every row aligned
+  const bool base16 = gm_aligned16(x) && gm_aligned16(g);
+  const bool al8 = base16 && (C % 8) == 0 && (xs % 8) == 0 && (gs % 8) == 0;
+  const bool al4 = base16 && (C % 4) == 0 && (xs % 4) == 0 && (gs % 4) == 0;
   if (x.scalar_type() == at::kBFloat16) {
     if (al8) LAUNCH(__hip_bfloat16, 8);
     else LAUNCH(__hip_bfloat16, 1);
@@ -157,10 +198,23 @@ std::vector<at::Tensor> gatemul_bwd(at::Tensor dy, at::Tensor x,
                                     c10::optional<at::Tensor> dg_out,
                                     long dxs, long dgs) {
   TORCH_CHECK(dy.is_contiguous(), "gatemul_bwd: dy must be contiguous");
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0,
+              "gatemul_bwd: x must be non-empty");
+  TORCH_CHECK(x.size(-1) == 1 || x.stride(-1) == 1,
+              "gatemul_bwd: x must be dense in its last dim");
+  gm_check_operand(g, x, "gatemul_bwd", "g");
+  gm_check_operand(dy, x, "gatemul_bwd", "dy");
+  TORCH_CHECK(dx_out.has_value() == dg_out.has_value(),
+              "gatemul_bwd: dx_out and dg_out must be given together");
   const int C = x.size(-1);
   const long rows = x.numel() / C;
+  const bool rm = rowmask.has_value();
+  const unsigned char* rm_ptr =
+      gm_check_rowmask(rowmask, x, rows, "gatemul_bwd");
   at::Tensor dx, dg;
   if (dx_out.has_value()) {
+    gm_check_operand(*dx_out, x, "gatemul_bwd", "dx_out");
+    gm_check_operand(*dg_out, x, "gatemul_bwd", "dg_out");
     dx = *dx_out;
     dg = *dg_out;
   } else {
@@ -170,9 +224,6 @@ std::vector<at::Tensor> gatemul_bwd(at::Tensor dy, at::Tensor x,
   }
   const int block = 256;
   auto stream = at::cuda::getCurrentHIPStream();
-  const bool rm = rowmask.has_value();
-  const unsigned char* rm_ptr =
-      rm ? rowmask->data_ptr<unsigned char>() : nullptr;
 
 #define LAUNCH_G2(T, VEC, GROUP, RM)                                        \
   hipLaunchKernelGGL((gatemul_bwd_kernel<T, VEC, GROUP, RM>),               \
@@ -195,9 +246,11 @@ std::vector<at::Tensor> gatemul_bwd(at::Tensor dy, at::Tensor x,
     else LAUNCH_G(T, VEC, 64);                                              \
   } while (0)
 
-  const bool al8 = (C % 8) == 0 && (xs % 8) == 0 && (gs % 8) == 0
+  const bool base16 = gm_aligned16(x) && gm_aligned16(g) &&
+      gm_aligned16(dy) && gm_aligned16(dx) && gm_aligned16(dg);
+  const bool al8 = base16 && (C % 8) == 0 && (xs % 8) == 0 && (gs % 8) == 0
       && (dxs % 8) == 0 && (dgs % 8) == 0;
-  const bool al4 = (C % 4) == 0 && (xs % 4) == 0 && (gs % 4) == 0
+  const bool al4 = base16 && (C % 4) == 0 && (xs % 4) == 0 && (gs % 4) == 0
       && (dxs % 4) == 0 && (dgs % 4) == 0;
   if (x.scalar_type() == at::kBFloat16) {
     if (al8) LAUNCH(__hip_bfloat16, 8);

@@ -183,10 +183,16 @@ def test_ddp_rccl_graph_rehearsal():
 
 
 def test_padded_batch_hip_eager_parity():
-    """End-to-end fwd+bwd on a PADDED batch: the fused attention zeroes
-    fully-masked query rows where eager propagates a uniform average
-    (documented deviation, docs/PARITY.md) — so parity is asserted at
-    VALID positions, and the loss (masked downstream) must match."""
+    """End-to-end fwd+bwd on a PADDED batch, HIP ops vs forced eager.
+
+    The model runs in fp32 WITHOUT autocast, and the fused attention
+    kernel is bf16-only, so attention takes the eager composition in
+    BOTH runs (dispatch warns about it): this test covers LayerNorm,
+    gating, GEGLU and the other fp32-capable HIP ops on a padded batch,
+    not the fused attention's "fully-masked rows output 0" deviation.
+    That is covered by tests/test_attention_paths.py (kernel level and
+    test_axial_attention_padded_runs_fused_kernel).  Parity is asserted
+    at VALID positions, and the loss (masked downstream) must match."""
     import os
     from alphafold2_amd import Alphafold2
     from alphafold2_amd.ops import dispatch
