@@ -9,8 +9,10 @@ state-dict layout (`attn.to_scalar_q`, `attn.point_weights`,
 
 Runs in fp32 (the structure module is pinned to fp32 for equivariance —
 reference alphafold2.py:607,855).  This is the K7 fusion target of
-SURVEY.md §2.17: all einsums below are shaped for a single fused fp32
-HIP kernel per refinement iteration.
+SURVEY.md §2.17: on the GPU the attention core (logits, masked softmax,
+aggregations, local-frame transform) runs as one fused fp32 HIP kernel
+per refinement iteration, with a fused backward for training; the
+einsum composition in `forward` is the CPU path and the reference.
 """
 import math
 
@@ -73,24 +75,23 @@ class InvariantPointAttention(nn.Module):
 
     def _fused_forward(self, x, pairwise_repr, rotations, translations,
                        mask):
-        """Inference-path fused fp32 IPA core (K7): one kernel for
-        logits + softmax + all aggregations (ops/hip/ipacore.hip,
-        HW-verified bit-exact by tools/ipa_probe.hip).  Returns None
-        when the configuration is outside the compiled constants or
-        gradients are required (training keeps eager autograd)."""
+        """Fused fp32 IPA core (K7), training and inference: one kernel
+        for logits + masked softmax + all aggregations, two for the
+        backward (ops/hip/ipacore.hip).  The projections, the
+        global-frame point transform, the softplus, the bias Linear and
+        `to_out` stay in Python autograd.  Returns None when
+        `dispatch.ipa_core_fusable` rejects the configuration (the
+        caller then runs the eager composition)."""
         from ..ops import dispatch as _dispatch
-        ok = (not torch.is_grad_enabled() and x.is_cuda
-              and self.require_pairwise_repr
-              and self.heads == 8 and self.scalar_key_dim == 16
-              and self.scalar_value_dim == 16
-              and self.point_key_dim == 4 and self.point_value_dim == 4
-              and pairwise_repr is not None
-              and pairwise_repr.shape[-1] == 256
-              and (mask is None or bool(mask.all()))
-              and _dispatch.using_hip(x, 'ipa_core_fwd'))
-        if not ok:
+        if not _dispatch.ipa_core_fusable(
+                x, pairwise_repr, heads=self.heads,
+                scalar_key_dim=self.scalar_key_dim,
+                scalar_value_dim=self.scalar_value_dim,
+                point_key_dim=self.point_key_dim,
+                point_value_dim=self.point_value_dim,
+                require_pairwise_repr=self.require_pairwise_repr):
             return None
-        ext = _dispatch._load_ext()
+        from ..ops import hip_autograd
         b, n, _ = x.shape
         h = self.heads
 
@@ -116,12 +117,15 @@ class InvariantPointAttention(nn.Module):
                     .permute(0, 3, 1, 2))
         point_w = F.softplus(self.point_weights).float().contiguous()
 
-        pieces = ext.ipa_core_fwd(
+        if mask is not None:
+            mask = mask.bool().expand(b, n)
+
+        pieces = hip_autograd.hip_ipa_core(
             q_s, k_s, v_s, q_pg, k_pg, v_pg, bias,
             f32c(pairwise_repr), f32c(rotations), f32c(translations),
             point_w, self.scalar_attn_logits_scale,
             self.pairwise_attn_logits_scale,
-            self.point_attn_logits_scale, self.eps)
+            self.point_attn_logits_scale, self.eps, mask)
         return self.to_out(pieces)
 
     def forward(self, single_repr, pairwise_repr=None, *, rotations,

@@ -241,6 +241,46 @@ def distance_buckets(coords, boundaries):
     return eager.distance_buckets(coords, boundaries)
 
 
+def ipa_core_fusable(x, pairwise_repr, *, heads, scalar_key_dim,
+                     scalar_value_dim, point_key_dim, point_value_dim,
+                     require_pairwise_repr):
+    """Gate of the fused IPA core (K7, forward and backward).  True when
+    `hip_autograd.hip_ipa_core` covers the configuration; otherwise the
+    caller runs the eager composition and, on a GPU with the extension
+    loaded, the failed predicate is named in a fallback warning.  Looks
+    at shapes and host-side device properties only: no device sync, so
+    the gate is safe inside hipGraph capture."""
+    if not _want_hip(x):
+        return False
+    ext = _load_ext()
+    n = x.shape[1]
+    pair_dim = pairwise_repr.shape[-1] if pairwise_repr is not None else 0
+    if not hasattr(ext, 'ipa_core_bwd'):
+        reason = 'extension built without ipa_core_bwd'
+    elif not require_pairwise_repr or pairwise_repr is None:
+        reason = 'require_pairwise_repr=False'
+    elif not 1 <= heads <= 8:
+        reason = f'heads={heads} (fused kernel covers 1 to 8)'
+    elif (scalar_key_dim, scalar_value_dim) != (16, 16):
+        reason = (f'scalar dims {scalar_key_dim}/{scalar_value_dim} '
+                  '(fused kernel covers 16/16)')
+    elif (point_key_dim, point_value_dim) != (4, 4):
+        reason = (f'point dims {point_key_dim}/{point_value_dim} '
+                  '(fused kernel covers 4/4)')
+    elif pair_dim % 64 != 0 or not 64 <= pair_dim <= 512:
+        reason = (f'pair dim {pair_dim} (fused kernel covers multiples '
+                  'of 64 up to 512)')
+    elif x.dtype == torch.float64:
+        reason = 'dtype=torch.float64 (fused kernel is fp32)'
+    elif n > ext.ipa_core_max_n(heads, pair_dim):
+        reason = (f'n={n} exceeds the LDS bound '
+                  f'{ext.ipa_core_max_n(heads, pair_dim)} for heads={heads}')
+    else:
+        return True
+    warn_gpu_fallback('ipa_core', reason)
+    return False
+
+
 def layer_norm(x, weight, bias, eps=1e-5):
     if using_hip(x, 'layernorm_fwd'):
         from .hip_autograd import hip_layer_norm

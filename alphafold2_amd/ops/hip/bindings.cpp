@@ -30,12 +30,20 @@ std::vector<at::Tensor> ff1_geglu_fwd(at::Tensor x, at::Tensor W,
                                       c10::optional<at::Tensor> bias,
                                       long stage, bool want_inter);
 at::Tensor wgrad(at::Tensor dY, at::Tensor X);
-at::Tensor ipa_core_fwd(at::Tensor q_s, at::Tensor k_s, at::Tensor v_s,
-                        at::Tensor q_pg, at::Tensor k_pg, at::Tensor v_pg,
-                        at::Tensor bias, at::Tensor pair, at::Tensor rot,
-                        at::Tensor trans, at::Tensor point_w,
-                        double scale_s, double scale_b, double scale_p,
-                        double eps);
+std::vector<at::Tensor> ipa_core_fwd(
+    at::Tensor q_s, at::Tensor k_s, at::Tensor v_s, at::Tensor q_pg,
+    at::Tensor k_pg, at::Tensor v_pg, at::Tensor bias, at::Tensor pair,
+    at::Tensor rot, at::Tensor trans, at::Tensor point_w, double scale_s,
+    double scale_b, double scale_p, double eps,
+    c10::optional<at::Tensor> mask, bool save_stats);
+std::vector<at::Tensor> ipa_core_bwd(
+    at::Tensor dout, at::Tensor attn, at::Tensor gpts, at::Tensor q_s,
+    at::Tensor k_s, at::Tensor v_s, at::Tensor q_pg, at::Tensor k_pg,
+    at::Tensor v_pg, at::Tensor bias, at::Tensor pair, at::Tensor rot,
+    at::Tensor trans, at::Tensor point_w, double scale_s, double scale_b,
+    double scale_p, double eps, c10::optional<at::Tensor> mask,
+    bool need_dpair, bool need_drot);
+long ipa_core_max_n(long heads, long pair_dim);
 at::Tensor pairrep_fwd(at::Tensor left, at::Tensor right, at::Tensor emb,
                        at::Tensor rel);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -82,7 +90,30 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(gfx950, K13)", py::arg("left"), py::arg("right"), py::arg("emb"),
         py::arg("rel"));
   m.def("ipa_core_fwd", &ipa_core_fwd,
-        "fused fp32 IPA attention core, inference path (gfx950, K7)");
+        "fused fp32 IPA attention core forward -> [out, attn, gpts]; attn "
+        "and gpts are saved for the backward only with save_stats "
+        "(gfx950, K7)",
+        py::arg("q_s"), py::arg("k_s"), py::arg("v_s"), py::arg("q_pg"),
+        py::arg("k_pg"), py::arg("v_pg"), py::arg("bias"), py::arg("pair"),
+        py::arg("rot"), py::arg("trans"), py::arg("point_w"),
+        py::arg("scale_s"), py::arg("scale_b"), py::arg("scale_p"),
+        py::arg("eps"), py::arg("mask") = c10::nullopt,
+        py::arg("save_stats") = false);
+  m.def("ipa_core_bwd", &ipa_core_bwd,
+        "fused fp32 IPA attention core backward: gradients of the eleven "
+        "core inputs, row-side + column-side kernels, no atomics "
+        "(gfx950, K7)",
+        py::arg("dout"), py::arg("attn"), py::arg("gpts"), py::arg("q_s"),
+        py::arg("k_s"), py::arg("v_s"), py::arg("q_pg"), py::arg("k_pg"),
+        py::arg("v_pg"), py::arg("bias"), py::arg("pair"), py::arg("rot"),
+        py::arg("trans"), py::arg("point_w"), py::arg("scale_s"),
+        py::arg("scale_b"), py::arg("scale_p"), py::arg("eps"),
+        py::arg("mask") = c10::nullopt, py::arg("need_dpair") = true,
+        py::arg("need_drot") = true);
+  m.def("ipa_core_max_n", &ipa_core_max_n,
+        "largest sequence length whose IPA core forward and backward fit "
+        "the device's LDS per block",
+        py::arg("heads"), py::arg("pair_dim") = 512);
   m.def("wgrad", &wgrad,
         "split-K weight-gradient GEMM dY^T @ X (gfx950 MFMA, fp32 out)",
         py::arg("dY"), py::arg("X"));

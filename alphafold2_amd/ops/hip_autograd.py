@@ -1,6 +1,7 @@
 """torch.autograd.Function wrappers around the gfx950 HIP kernels."""
 import torch
 from torch.amp import custom_bwd, custom_fwd
+from torch.autograd.function import once_differentiable
 
 from .dispatch import _load_ext
 
@@ -566,6 +567,58 @@ class _TriProjGatesFn(torch.autograd.Function):
 
 def hip_tri_proj_gates(fused, hdim, rowmask=None):
     return _TriProjGatesFn.apply(fused, hdim, rowmask)
+
+
+class _IPACoreFn(torch.autograd.Function):
+    """Fused fp32 IPA attention core (K7): logits + masked softmax + the
+    three value aggregations + local-frame transform in one kernel.
+    When a gradient is required the forward also saves the
+    probabilities (b,h,n,n) and the aggregated global points; the
+    backward is a row-side plus a column-side kernel without atomics.
+    dpair and drot are only computed when their inputs require grad."""
+
+    @staticmethod
+    @custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, q_s, k_s, v_s, q_pg, k_pg, v_pg, bias, pair, rot,
+                trans, point_w, mask, scales):
+        ext = _load_ext()
+        tensors = tuple(t.contiguous() for t in (
+            q_s, k_s, v_s, q_pg, k_pg, v_pg, bias, pair, rot, trans,
+            point_w))
+        mask_c = mask.contiguous() if mask is not None else None
+        save = any(ctx.needs_input_grad)
+        out, attn, gpts = ext.ipa_core_fwd(*tensors, *scales, mask=mask_c,
+                                           save_stats=save)
+        if save:
+            ctx.save_for_backward(attn, gpts, *tensors)
+            ctx.mask = mask_c
+            ctx.scales = scales
+        return out
+
+    @staticmethod
+    @custom_bwd(device_type='cuda')
+    @once_differentiable
+    def backward(ctx, dout):
+        ext = _load_ext()
+        attn, gpts, *tensors = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = ext.ipa_core_bwd(dout.contiguous(), attn, gpts, *tensors,
+                                 *ctx.scales, mask=ctx.mask,
+                                 need_dpair=need[7], need_drot=need[8])
+        return (*(g if n else None for g, n in zip(grads, need)),
+                None, None)
+
+
+def hip_ipa_core(q_s, k_s, v_s, q_pg, k_pg, v_pg, bias, pair, rot, trans,
+                 point_w, scale_s, scale_b, scale_p, eps, mask=None):
+    """q_s/k_s/v_s (b,n,h,16), q_pg/k_pg/v_pg (b,n,h,4,3) in the global
+    frame, bias (b,h,n,n), pair (b,n,n,dp), rot (b,n,3,3), trans (b,n,3),
+    point_w (h,) softplus-ed, mask (b,n) bool or None.  Returns the
+    (b, n, h*(16 + dp + 16)) concatenation `to_out` consumes."""
+    return _IPACoreFn.apply(q_s, k_s, v_s, q_pg, k_pg, v_pg, bias, pair,
+                            rot, trans, point_w, mask,
+                            (float(scale_s), float(scale_b), float(scale_p),
+                             float(eps)))
 
 
 class _PairRepFn(torch.autograd.Function):
