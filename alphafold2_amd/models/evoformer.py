@@ -130,13 +130,15 @@ class Attention(nn.Module):
             inner = self.to_q.weight.shape[0]
             fused = F.linear(x, w, bias_cat)
 
-            if tie_dim is None and not (self.dropout_p > 0 and self.training):
+            if tie_dim is None:
                 # packed fast path: the fused kernel consumes q/k/v as
                 # strided slices and writes one packed grad (no
-                # split-backward concatenation)
+                # split-backward concatenation); attention-prob dropout
+                # runs inside the kernels
                 out = ops.attention_core_packed(
                     fused, h, inner, bias=attn_bias, mask=mask,
-                    bias_repeat=attn_bias_repeat)
+                    bias_repeat=attn_bias_repeat, dropout=self.dropout_p,
+                    training=self.training)
                 if out is not None:
                     out = out.transpose(-2, -3).reshape(*x.shape[:-1], -1)
                     gates = fused.narrow(-1, 3 * inner, inner)

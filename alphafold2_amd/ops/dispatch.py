@@ -81,36 +81,58 @@ def warn_gpu_fallback(opname: str, reason: str):
 # op entry points
 
 
+def _attn_unfusable_reason(t, dim_head, bias, drop_p, tie_dim=None,
+                           batch=None):
+    """None when the fused attention kernels cover the configuration,
+    else the text naming the predicate that failed.  `t` is the bf16
+    q (or packed) tensor; drop_p the ACTIVE dropout rate (0 when off).
+    A missing extension is not judged here (`_want_hip` raises or allows
+    eager for it)."""
+    ext = _load_ext()
+    if ext is not None and not hasattr(ext, 'attn_fwd'):
+        return 'extension built without attn_fwd'
+    if (ext is not None and drop_p > 0.
+            and not hasattr(ext, 'attn_dropout_mask')):
+        return ('attention-prob dropout active and the extension was built '
+                'without attn_dropout_mask')
+    if drop_p >= 1.:
+        return f'attention-prob dropout p={drop_p} (fused kernel needs p < 1)'
+    if not (dim_head <= 64 and dim_head % 8 == 0):
+        return (f'dim_head={dim_head} (fused kernel covers '
+                'multiples of 8 up to 64)')
+    if t.dtype != torch.bfloat16:
+        return f'dtype={t.dtype} (fused kernel is bf16)'
+    if bias is not None and bias.dtype != torch.bfloat16:
+        return f'bias dtype={bias.dtype} (fused kernel is bf16)'
+    if tie_dim is not None and batch % tie_dim != 0:
+        return f'batch {batch} is not divisible by tie_dim={tie_dim}'
+    return None
+
+
 def attention_core(q, k, v, bias=None, mask=None, context_mask=None,
                    tie_dim=None, bias_repeat=1, dropout=0., training=False):
     """bias (when given) has shape (B // bias_repeat, h, Lq, Lk); the
     repeat fold is resolved inside the fused kernel (never materialized),
     and expanded explicitly only on the eager path.  Attention-prob
-    dropout (reference alphafold2.py:172) routes to the eager path."""
-    drop_active = dropout > 0. and training
+    dropout (reference alphafold2.py:172) runs inside the fused kernels
+    when `dropout > 0 and training`."""
+    drop_p = float(dropout) if (dropout > 0. and training) else 0.
     # head dims < 64 run on the 64-wide tile via zero padding (see
     # hip_attention_core); only dim_head > 64 or non-multiple-of-8
     # layouts fall back to eager
-    fusable = (
-        not drop_active
-        and q.dtype == torch.bfloat16
-        and q.shape[-1] <= 64 and q.shape[-1] % 8 == 0
-        and (bias is None or bias.dtype == torch.bfloat16)
-        and (tie_dim is None or q.shape[0] % tie_dim == 0)
-        and using_hip(q, 'attn_fwd')
-    )
-    if fusable:
-        from .hip_autograd import hip_attention_core
-        return hip_attention_core(q, k, v, bias=bias, mask=mask,
-                                  context_mask=context_mask,
-                                  tie_dim=tie_dim, bias_repeat=bias_repeat)
-    if q.is_cuda and hip_ops_available() and not _FORCE_EAGER:
-        reason = ('attention-prob dropout active' if drop_active
-                  else f'dim_head={q.shape[-1]} (fused kernel covers '
-                       'multiples of 8 up to 64)'
-                  if not (q.shape[-1] <= 64 and q.shape[-1] % 8 == 0)
-                  else f'dtype={q.dtype} (fused kernel is bf16)')
-        warn_gpu_fallback('attention_core', reason)
+    if q.is_cuda and not _FORCE_EAGER:
+        reason = _attn_unfusable_reason(q, q.shape[-1], bias, drop_p,
+                                        tie_dim, q.shape[0])
+        if reason is not None:
+            if hip_ops_available():
+                warn_gpu_fallback('attention_core', reason)
+        elif _want_hip(q):
+            from .hip_autograd import hip_attention_core
+            return hip_attention_core(q, k, v, bias=bias, mask=mask,
+                                      context_mask=context_mask,
+                                      tie_dim=tie_dim,
+                                      bias_repeat=bias_repeat,
+                                      dropout_p=drop_p)
     if bias is not None and bias_repeat != 1:
         bias = bias.repeat_interleave(bias_repeat, dim=0)
     return eager.attention_core(q, k, v, bias=bias, mask=mask,
@@ -119,23 +141,25 @@ def attention_core(q, k, v, bias=None, mask=None, context_mask=None,
 
 
 def attention_core_packed(packed, heads, inner, bias=None, mask=None,
-                          context_mask=None, bias_repeat=1):
+                          context_mask=None, bias_repeat=1, dropout=0.,
+                          training=False):
     """Self-attention consuming a packed [q|k|v|...] projection (B, L, W).
     HIP-only fast path; returns None if not fusable (caller falls back
-    to the split path)."""
+    to the split path, whose dispatch names the reason)."""
     key_mask = context_mask if context_mask is not None else mask
+    drop_p = float(dropout) if (dropout > 0. and training) else 0.
     fusable = (
-        packed.dtype == torch.bfloat16
+        packed.is_cuda
         and (inner // heads) == 64
-        and (bias is None or bias.dtype == torch.bfloat16)
-        and packed.is_cuda
-        and using_hip(packed, 'attn_fwd')
+        and _attn_unfusable_reason(packed, 64, bias, drop_p) is None
+        and _want_hip(packed)
     )
     if not fusable:
         return None
     from .hip_autograd import hip_attention_packed
     return hip_attention_packed(packed, heads, inner, bias=bias,
-                                mask=key_mask, bias_repeat=bias_repeat)
+                                mask=key_mask, bias_repeat=bias_repeat,
+                                dropout_p=drop_p)
 
 
 def geglu(x):

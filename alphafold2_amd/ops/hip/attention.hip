@@ -32,7 +32,10 @@
 //    16-byte ds_read per fragment).
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
+#include <ATen/hip/HIPGeneratorImpl.h>
+#include <ATen/hip/HIPGraphsUtils.cuh>
 
+#include "attn_dropout.h"
 #include "common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -354,16 +357,43 @@ __device__ __forceinline__ float rowred_sum(const f32x4 s[4], int reg) {
 constexpr int FBQ = 128;    // fwd query rows per workgroup
 constexpr int FNT = 512;    // fwd threads (8 waves x 16 q rows)
 
-template <bool HAS_BIAS, bool HAS_MASK>
+// Attention-probability dropout operands (attn_dropout.h).  The
+// HAS_DROP = false specialisations are empty, so those instantiations
+// keep the kernel arguments and the code they had without dropout.
+template <bool HAS_DROP> struct FwdDrop {};
+template <> struct FwdDrop<true> {
+  at::PhiloxCudaState philox;  // drawn from the generator (graph-safe) ...
+  const int64_t* state_in;     // ... unless the caller gave (seed, offset)
+  int64_t* state_out;          // (seed, offset) handed on to the backward
+  uint32_t thresh;
+  float rescale;
+};
+template <bool HAS_DROP> struct BwdDrop {};
+template <> struct BwdDrop<true> {
+  const int64_t* state;        // (seed, offset) the forward used
+  uint32_t thresh;
+  float rescale;
+};
+
+__device__ __forceinline__ attn_drop::Params drop_params(
+    const BwdDrop<true>& d, int Lq, int Lk) {
+  return attn_drop::Params{(uint64_t)d.state[0], (uint64_t)d.state[1],
+                           d.thresh, d.rescale, (Lq + 3) >> 2, (Lk + 3) >> 2};
+}
+
+template <bool HAS_BIAS, bool HAS_MASK, bool HAS_DROP>
 // minWavesPerEU=4 caps VGPRs at 128: the <bias,mask> variant was
-// 129 VGPRs = 3 waves/SIMD = only ONE 8-wave block resident per CU
-__global__ __launch_bounds__(FNT, 4)
+// 129 VGPRs = 3 waves/SIMD = only ONE 8-wave block resident per CU.
+// The HAS_DROP variants need ~20 more live registers for the Philox
+// rounds and would spill under that cap: they take the uncapped
+// allocation (one resident block) instead of scratch traffic.
+__global__ __launch_bounds__(FNT, HAS_DROP ? 2 : 4)
 void attn_fwd_kernel(TView q, TView k, TView v,
                      const bf16_t* __restrict__ bias,
                      const unsigned char* __restrict__ mask,
                      TViewMut out, float* __restrict__ lse,
                      int Lq, int Lk, int heads, int bias_repeat, int q_repeat,
-                     float scale) {
+                     float scale, FwdDrop<HAS_DROP> drop) {
   __shared__ char q_lds[FBQ * ROWB];
   // K / V^T / mask tiles are DOUBLE-buffered so the loop needs a single
   // __syncthreads per KV tile (placed between store and compute): the
@@ -390,6 +420,25 @@ void attn_fwd_kernel(TView q, TView k, TView v,
     const int bias_batch = batch / bias_repeat;
     bias_g = bias + ((long)(bias_batch * heads + head) * Lq
                      + (long)qtile * FBQ) * Lk;
+  }
+
+  attn_drop::Params dpar{};
+  if constexpr (HAS_DROP) {
+    uint64_t seed, offset;
+    if (drop.state_in != nullptr) {
+      seed = (uint64_t)drop.state_in[0];
+      offset = (uint64_t)drop.state_in[1];
+    } else {
+      auto so = at::cuda::philox::unpack(drop.philox);
+      seed = std::get<0>(so);
+      offset = std::get<1>(so);
+      if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+        drop.state_out[0] = (int64_t)seed;
+        drop.state_out[1] = (int64_t)offset;
+      }
+    }
+    dpar = attn_drop::Params{seed, offset, drop.thresh, drop.rescale,
+                             (Lq + 3) >> 2, (Lk + 3) >> 2};
   }
 
   const int q_rows = min(FBQ, Lq - qtile * FBQ);
@@ -439,6 +488,16 @@ void attn_fwd_kernel(TView q, TView k, TView v,
                                 next_rows, vreg);
     }
     __syncthreads();
+
+    // this tile's 16 keep bits per lane, generated here where the fewest
+    // registers are live (no S tile yet); the integer work overlaps the
+    // LDS reads of the first MFMAs
+    uint32_t kb = 0;
+    if constexpr (HAS_DROP) {
+      kb = attn_drop::keep_bits_c_layout<true>(
+          dpar, bh, (qtile * FBQ + wave * 16 + (lane >> 4) * 4) >> 2, t * BK,
+          lane);
+    }
 
     // S = Q K^T  (16 q x 64 kv per wave); setprio favors the MFMA
     // cluster when co-resident waves are staging (guide T5)
@@ -497,6 +556,19 @@ void attn_fwd_kernel(TView q, TView k, TView v,
       m_i[reg] = m_new[reg];
 #pragma unroll
       for (int c = 0; c < 4; ++c) o_acc[c][reg] *= alpha[reg];
+    }
+
+    // dropout after the softmax statistics: m_i and l_i (and lse) are
+    // those of the undropped probabilities, only the P.V operand drops
+    if constexpr (HAS_DROP) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          s[c][reg] = ((kb >> (c * 4 + reg)) & 1u)
+              ? s[c][reg] * dpar.rescale : 0.f;
+        }
+      }
     }
 
     // P tile -> per-wave swizzled LDS scratch (C layout -> A layout)
@@ -586,10 +658,11 @@ __global__ void attn_delta_kernel(TView dout, TView out,
 // ---------------------------------------------------------------------------
 // backward dQ: loop kv tiles; dS = P*(dP - delta)*scale; dQ += dS K
 
-template <bool HAS_BIAS, bool HAS_MASK>
+template <bool HAS_BIAS, bool HAS_MASK, bool HAS_DROP>
 // minWavesPerEU=3 caps VGPRs at 170 (the <bias,mask> variant was 178
-// -> 2 waves/SIMD); 3 waves = 3 resident 4-wave blocks per CU
-__global__ __launch_bounds__(256, 3)
+// -> 2 waves/SIMD); 3 waves = 3 resident 4-wave blocks per CU.
+// HAS_DROP variants: uncapped, see attn_fwd_kernel.
+__global__ __launch_bounds__(256, HAS_DROP ? 2 : 3)
 void attn_bwd_dq_kernel(TView q, TView k, TView v,
                         const bf16_t* __restrict__ bias,
                         const unsigned char* __restrict__ mask,
@@ -598,7 +671,7 @@ void attn_bwd_dq_kernel(TView q, TView k, TView v,
                         const float* __restrict__ delta,
                         TViewMut dq,
                         int Lq, int Lk, int heads, int bias_repeat, int q_repeat,
-                        float scale) {
+                        float scale, BwdDrop<HAS_DROP> drop) {
   __shared__ char q_lds[BQ * ROWB];
   __shared__ char do_lds[BQ * ROWB];
   __shared__ char k_lds[BK * ROWB];
@@ -606,6 +679,9 @@ void attn_bwd_dq_kernel(TView q, TView k, TView v,
   __shared__ char v_lds[BK * ROWB];
   __shared__ char s_lds[NWAVES][16 * ROWB];
   __shared__ unsigned char m_lds[BK];
+
+  attn_drop::Params dpar{};
+  if constexpr (HAS_DROP) dpar = drop_params(drop, Lq, Lk);
 
   const int qtile = blockIdx.x;
   const int bh = blockIdx.y;
@@ -674,6 +750,14 @@ void attn_bwd_dq_kernel(TView q, TView k, TView v,
       stage_load(v_g + (long)(t + 1) * BK * v.rs, v.rs, next_rows, vreg);
     }
 
+    // this tile's keep bits, generated before the S and dP tiles are live
+    uint32_t kb = 0;
+    if constexpr (HAS_DROP) {
+      kb = attn_drop::keep_bits_c_layout<true>(
+          dpar, bh, (qtile * BQ + wave * 16 + (lane >> 4) * 4) >> 2, t * BK,
+          lane);
+    }
+
     // recompute S then P = exp(S*scale + bias - lse)
     f32x4 p[4], dp[4];
 #pragma unroll
@@ -721,6 +805,19 @@ void attn_bwd_dq_kernel(TView q, TView k, TView v,
                                                       0, 0, 0);
       }
       dp[c] = acc;
+    }
+
+    // dropped forward: O = (keep * rescale * P) V, so dP carries the
+    // same factor and delta = rowsum(dO * O) is still sum_j P dP
+    if constexpr (HAS_DROP) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          dp[c][reg] = ((kb >> (c * 4 + reg)) & 1u)
+              ? dp[c][reg] * dpar.rescale : 0.f;
+        }
+      }
     }
 
     // dS = P * (dP - delta) * scale  -> bf16 via LDS scratch
@@ -779,7 +876,7 @@ void attn_bwd_dq_kernel(TView q, TView k, TView v,
 //   S^T = K Q^T,  P^T,  dV += P^T dO,  dP^T = V dO^T,
 //   dS^T = P^T (dP^T - delta) scale,  dK += dS^T Q.
 
-template <bool HAS_BIAS, bool HAS_MASK, bool NEED_DBIAS>
+template <bool HAS_BIAS, bool HAS_MASK, bool NEED_DBIAS, bool HAS_DROP>
 __global__ __launch_bounds__(256, 2)
 void attn_bwd_dkv_kernel(TView q, TView k, TView v,
                          const bf16_t* __restrict__ bias,
@@ -791,7 +888,7 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
                          float* __restrict__ dbias,
                          int dbias_chunks, long dbias_stride,
                          int Lq, int Lk, int heads, int bias_repeat, int q_repeat,
-                         float scale) {
+                         float scale, BwdDrop<HAS_DROP> drop) {
   __shared__ char k_lds[BK * ROWB];
   __shared__ char v_lds[BK * ROWB];
   __shared__ char q_lds[BQ * ROWB];
@@ -803,6 +900,9 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
   __shared__ float lse_lds[BQ];
   __shared__ float delta_lds[BQ];
   __shared__ unsigned char m_lds[BK];
+
+  attn_drop::Params dpar{};
+  if constexpr (HAS_DROP) dpar = drop_params(drop, Lq, Lk);
 
   const int ktile = blockIdx.x;
   const int bh = blockIdx.y;
@@ -921,7 +1021,17 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
       }
     }
 
+    // keep bits of this wave's (kv rows) x (q cols) transposed tile
+    uint32_t kb = 0;
+    if constexpr (HAS_DROP) {
+      kb = attn_drop::keep_bits_c_layout<false>(
+          dpar, bh, (ktile * BK + wave * 16 + (lane >> 4) * 4) >> 2, t * BQ,
+          lane);
+    }
+
     // dV += P^T dO : A = P^T (k = q, via LDS), B col = dv, k = q
+    // (with dropout the operand is keep * rescale * P^T; pt itself stays
+    // undropped for dS^T below)
     char* sw = s_lds[wave];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
@@ -929,8 +1039,11 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const int row = (lane >> 4) * 4 + reg;
+        float pv = pt[c][reg];
+        if constexpr (HAS_DROP)
+          pv = ((kb >> (c * 4 + reg)) & 1u) ? pv * dpar.rescale : 0.f;
         *reinterpret_cast<bf16_t*>(sw + swz(row, col * (int)sizeof(bf16_t)))
-            = (bf16_t)pt[c][reg];
+            = (bf16_t)pv;
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -963,6 +1076,16 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
                                                       0, 0, 0);
       }
       dpt[c] = acc;
+    }
+    if constexpr (HAS_DROP) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+#pragma unroll
+        for (int reg = 0; reg < 4; ++reg) {
+          dpt[c][reg] = ((kb >> (c * 4 + reg)) & 1u)
+              ? dpt[c][reg] * dpar.rescale : 0.f;
+        }
+      }
     }
 
     // dS^T = P^T (dP^T - delta[q]) scale ; emit dBias; stage for dK
@@ -1413,6 +1536,25 @@ void attn_bwd_dk_kernel(TView q, TView k, TView v,
   }
 }
 
+// ---------------------------------------------------------------------------
+// dropout keep mask as a tensor (tests, debugging): one element per
+// thread through the per-element form of the shared function
+
+__global__ void attn_dropout_mask_kernel(const int64_t* __restrict__ state,
+                                         unsigned char* __restrict__ keep,
+                                         int Lq, int Lk, long total,
+                                         uint32_t thresh) {
+  const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const attn_drop::Params p{(uint64_t)state[0], (uint64_t)state[1], thresh,
+                            0.f, (Lq + 3) >> 2, (Lk + 3) >> 2};
+  const int j = (int)(idx % Lk);
+  const long bi = idx / Lk;
+  const int i = (int)(bi % Lq);
+  const int bh = (int)(bi / Lq);
+  keep[idx] = attn_drop::keep(p, bh, i, j) ? 1 : 0;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -1478,16 +1620,38 @@ void check_qkv_bias(const at::Tensor& q, const at::Tensor& k,
   }
 }
 
+void check_dropout_p(double p, const char* fn) {
+  TORCH_CHECK(p > 0.0 && p < 1.0, fn, ": dropout_p must satisfy 0 < p < 1, "
+              "got ", p);
+}
+
+// (seed, offset) as the kernels read it: int64[2] on q's device
+void check_rng_state(const at::Tensor& s, const at::Tensor& q,
+                     const char* fn) {
+  TORCH_CHECK(s.scalar_type() == at::kLong && s.numel() == 2 &&
+              s.is_contiguous(), fn,
+              ": rng_state must be a contiguous int64 tensor of 2 elements "
+              "(seed, offset), got ", s.scalar_type(), " ", s.sizes());
+  TORCH_CHECK(s.device() == q.device(), fn,
+              ": rng_state must be on q's device");
+}
+
 }  // namespace
 
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  c10::optional<at::Tensor> bias,
                                  c10::optional<at::Tensor> mask,
                                  long bias_repeat, double scale,
-                                 long q_repeat) {
+                                 long q_repeat, double dropout_p,
+                                 c10::optional<at::Tensor> rng_state) {
   TORCH_CHECK(q.scalar_type() == at::kBFloat16, "attn_fwd: bf16 only");
   check_qkv_bias(q, k, v, bias, bias_repeat, q_repeat, "attn_fwd");
   const int B = k.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
+  const bool has_drop = dropout_p != 0.0;
+  if (has_drop) {
+    check_dropout_p(dropout_p, "attn_fwd");
+    if (rng_state.has_value()) check_rng_state(*rng_state, q, "attn_fwd");
+  }
 
   // out in (B, Lq, H, DH) memory (the layout downstream Linears want),
   // exposed as a (B, H, Lq, DH) strided view
@@ -1514,20 +1678,74 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
   TView qv = make_view(q), kv = make_view(k), vv = make_view(v);
   TViewMut ov = make_view_mut(out);
 
-#define DISPATCH(HB, HM)                                                      \
-  hipLaunchKernelGGL((attn_fwd_kernel<HB, HM>), grid, dim3(FNT), 0, stream,   \
-      qv, kv, vv,                                                             \
+#define DISPATCH(HB, HM, HD, DROP)                                            \
+  hipLaunchKernelGGL((attn_fwd_kernel<HB, HM, HD>), grid, dim3(FNT), 0,       \
+      stream, qv, kv, vv,                                                     \
       has_bias ? reinterpret_cast<const bf16_t*>(bias_c.data_ptr()) : nullptr,\
       has_mask ? mask_u8.data_ptr<unsigned char>() : nullptr,                 \
       ov, lse.data_ptr<float>(),                                              \
-      Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale)
+      Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale, DROP)
 
-  if (has_bias && has_mask) DISPATCH(true, true);
-  else if (has_bias) DISPATCH(true, false);
-  else if (has_mask) DISPATCH(false, true);
-  else DISPATCH(false, false);
+  if (!has_drop) {
+    const FwdDrop<false> nd{};
+    if (has_bias && has_mask) DISPATCH(true, true, false, nd);
+    else if (has_bias) DISPATCH(true, false, false, nd);
+    else if (has_mask) DISPATCH(false, true, false, nd);
+    else DISPATCH(false, false, false, nd);
+    return {out, lse};
+  }
+
+  FwdDrop<true> dr{};
+  dr.thresh = attn_drop::threshold(dropout_p);
+  dr.rescale = attn_drop::rescale(dr.thresh);
+  at::Tensor state;
+  if (rng_state.has_value()) {
+    state = *rng_state;
+    dr.state_in = state.data_ptr<int64_t>();
+    dr.state_out = nullptr;
+  } else {
+    // each 4x4 block is its own subsequence and uses one 128-bit output
+    // (4 values); the PhiloxCudaState goes to the kernel by value and is
+    // unpacked there, which keeps a captured graph correct on replay
+    auto gen = at::get_generator_or_default<at::CUDAGeneratorImpl>(
+        c10::nullopt, at::cuda::detail::getDefaultCUDAGenerator());
+    {
+      std::lock_guard<std::mutex> lock(gen->mutex_);
+      dr.philox = gen->philox_cuda_state(4);
+    }
+    state = at::empty({2}, q.options().dtype(at::kLong));
+    dr.state_in = nullptr;
+    dr.state_out = state.data_ptr<int64_t>();
+  }
+  if (has_bias && has_mask) DISPATCH(true, true, true, dr);
+  else if (has_bias) DISPATCH(true, false, true, dr);
+  else if (has_mask) DISPATCH(false, true, true, dr);
+  else DISPATCH(false, false, true, dr);
 #undef DISPATCH
-  return {out, lse};
+  return {out, lse, state};
+}
+
+at::Tensor attn_dropout_mask(at::Tensor rng_state, long B, long H, long Lq,
+                             long Lk, double dropout_p) {
+  check_dropout_p(dropout_p, "attn_dropout_mask");
+  check_rng_state(rng_state, rng_state, "attn_dropout_mask");
+  TORCH_CHECK(rng_state.is_cuda(), "attn_dropout_mask: rng_state must be on "
+              "the GPU");
+  TORCH_CHECK(B > 0 && H > 0 && Lq > 0 && Lk > 0,
+              "attn_dropout_mask: B, H, Lq and Lk must be positive");
+  auto keep = at::empty({B, H, Lq, Lk},
+                        rng_state.options().dtype(at::kByte));
+  const long total = keep.numel();
+  const int block = 256;
+  const long grid = (total + block - 1) / block;
+  TORCH_CHECK(B * H <= INT_MAX && grid <= INT_MAX,
+              "attn_dropout_mask: shape too large");
+  hipLaunchKernelGGL(attn_dropout_mask_kernel, dim3(grid), dim3(block), 0,
+                     at::cuda::getCurrentHIPStream(),
+                     rng_state.data_ptr<int64_t>(),
+                     keep.data_ptr<unsigned char>(), (int)Lq, (int)Lk, total,
+                     attn_drop::threshold(dropout_p));
+  return keep;
 }
 
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
@@ -1538,8 +1756,22 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  bool need_dbias, long q_repeat,
                                  c10::optional<at::Tensor> dq_out,
                                  c10::optional<at::Tensor> dk_out,
-                                 c10::optional<at::Tensor> dv_out) {
+                                 c10::optional<at::Tensor> dv_out,
+                                 double dropout_p,
+                                 c10::optional<at::Tensor> rng_state) {
   check_qkv_bias(q, k, v, bias, bias_repeat, q_repeat, "attn_bwd");
+  const bool has_drop = dropout_p != 0.0;
+  BwdDrop<true> dr{};
+  if (has_drop) {
+    check_dropout_p(dropout_p, "attn_bwd");
+    TORCH_CHECK(rng_state.has_value(),
+                "attn_bwd: dropout_p > 0 requires the forward's rng_state");
+    check_rng_state(*rng_state, q, "attn_bwd");
+    dr.state = rng_state->data_ptr<int64_t>();
+    dr.thresh = attn_drop::threshold(dropout_p);
+    dr.rescale = attn_drop::rescale(dr.thresh);
+  }
+  const BwdDrop<false> nd{};
   const int B = k.size(0), H = q.size(1), Lq = q.size(2), Lk = k.size(2);
   check_bf16(dout, q, "attn_bwd", "dout");
   check_bf16(out, q, "attn_bwd", "out");
@@ -1621,28 +1853,35 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   dim3 grid_k((Lk + BK - 1) / BK, B * H);
 
 #define DISPATCH_DQ(HB, HM)                                                   \
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<HB, HM>), grid_q, dim3(256), 0,      \
+  if (has_drop) DISPATCH_DQ_(HB, HM, true, dr);                               \
+  else DISPATCH_DQ_(HB, HM, false, nd)
+#define DISPATCH_DQ_(HB, HM, HD, DROP)                                        \
+  hipLaunchKernelGGL((attn_bwd_dq_kernel<HB, HM, HD>), grid_q, dim3(256), 0,  \
       stream, qv, kvv, vv,                                                    \
       has_bias ? reinterpret_cast<const bf16_t*>(bias_c.data_ptr()) : nullptr,\
       has_mask ? mask_u8.data_ptr<unsigned char>() : nullptr,                 \
       dov, lse.data_ptr<float>(), delta.data_ptr<float>(), dqv,               \
-      Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale)
+      Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale, DROP)
 
-  if (has_bias && has_mask) DISPATCH_DQ(true, true);
-  else if (has_bias) DISPATCH_DQ(true, false);
-  else if (has_mask) DISPATCH_DQ(false, true);
-  else DISPATCH_DQ(false, false);
+  if (has_bias && has_mask) { DISPATCH_DQ(true, true); }
+  else if (has_bias) { DISPATCH_DQ(true, false); }
+  else if (has_mask) { DISPATCH_DQ(false, true); }
+  else { DISPATCH_DQ(false, false); }
 #undef DISPATCH_DQ
+#undef DISPATCH_DQ_
 
 #define DISPATCH_DKV(HB, HM, DB)                                              \
-  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HB, HM, DB>), grid_k, dim3(256), 0, \
-      stream, qv, kvv, vv,                                                    \
+  if (has_drop) DISPATCH_DKV_(HB, HM, DB, true, dr);                          \
+  else DISPATCH_DKV_(HB, HM, DB, false, nd)
+#define DISPATCH_DKV_(HB, HM, DB, HD, DROP)                                   \
+  hipLaunchKernelGGL((attn_bwd_dkv_kernel<HB, HM, DB, HD>), grid_k,           \
+      dim3(256), 0, stream, qv, kvv, vv,                                      \
       has_bias ? reinterpret_cast<const bf16_t*>(bias_c.data_ptr()) : nullptr,\
       has_mask ? mask_u8.data_ptr<unsigned char>() : nullptr,                 \
       dov, lse.data_ptr<float>(), delta.data_ptr<float>(), dkv, dvv,          \
       DB ? dbias.data_ptr<float>() : nullptr,                                 \
       dbias_chunks, need_dbias ? dbias.stride(0) : 0L,                        \
-      Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale)
+      Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale, DROP)
 
 #define DISPATCH_DV(HB, HM)                                                   \
   hipLaunchKernelGGL((attn_bwd_dv_kernel<HB, HM>), grid_k, dim3(256), 0,      \
@@ -1671,7 +1910,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     return e != nullptr && e[0] == '1';
   }();
 
-  if (split_dkv) {
+  // the split kernels do not know dropout: with it, always combined
+  if (split_dkv && !has_drop) {
     if (has_bias && has_mask) DISPATCH_DV(true, true);
     else if (has_bias) DISPATCH_DV(true, false);
     else if (has_mask) DISPATCH_DV(false, true);
@@ -1685,14 +1925,15 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     else DISPATCH_DK(false, false, false);
   } else {
     if (need_dbias) {
-      if (has_mask) DISPATCH_DKV(true, true, true);
-      else DISPATCH_DKV(true, false, true);
-    } else if (has_bias && has_mask) DISPATCH_DKV(true, true, false);
-    else if (has_bias) DISPATCH_DKV(true, false, false);
-    else if (has_mask) DISPATCH_DKV(false, true, false);
-    else DISPATCH_DKV(false, false, false);
+      if (has_mask) { DISPATCH_DKV(true, true, true); }
+      else { DISPATCH_DKV(true, false, true); }
+    } else if (has_bias && has_mask) { DISPATCH_DKV(true, true, false); }
+    else if (has_bias) { DISPATCH_DKV(true, false, false); }
+    else if (has_mask) { DISPATCH_DKV(false, true, false); }
+    else { DISPATCH_DKV(false, false, false); }
   }
 #undef DISPATCH_DKV
+#undef DISPATCH_DKV_
 #undef DISPATCH_DV
 #undef DISPATCH_DK
 

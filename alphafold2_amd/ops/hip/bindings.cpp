@@ -50,7 +50,10 @@ std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  c10::optional<at::Tensor> bias,
                                  c10::optional<at::Tensor> mask,
                                  long bias_repeat, double scale,
-                                 long q_repeat);
+                                 long q_repeat, double dropout_p,
+                                 c10::optional<at::Tensor> rng_state);
+at::Tensor attn_dropout_mask(at::Tensor rng_state, long B, long H, long Lq,
+                             long Lk, double dropout_p);
 std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  at::Tensor v, at::Tensor out, at::Tensor lse,
                                  c10::optional<at::Tensor> bias,
@@ -59,7 +62,9 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  bool need_dbias, long q_repeat,
                                  c10::optional<at::Tensor> dq_out,
                                  c10::optional<at::Tensor> dk_out,
-                                 c10::optional<at::Tensor> dv_out);
+                                 c10::optional<at::Tensor> dv_out,
+                                 double dropout_p,
+                                 c10::optional<at::Tensor> rng_state);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd, "fused LayerNorm forward (gfx950)");
@@ -120,12 +125,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attn_fwd", &attn_fwd, "fused flash attention forward (gfx950)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"),
         py::arg("mask"), py::arg("bias_repeat"), py::arg("scale"),
-        py::arg("q_repeat") = 1);
+        py::arg("q_repeat") = 1, py::arg("dropout_p") = 0.0,
+        py::arg("rng_state") = c10::nullopt);
+  m.def("attn_dropout_mask", &attn_dropout_mask,
+        "keep mask (B, H, Lq, Lk) uint8 of the fused attention dropout",
+        py::arg("rng_state"), py::arg("B"), py::arg("H"), py::arg("Lq"),
+        py::arg("Lk"), py::arg("dropout_p"));
   m.def("attn_bwd", &attn_bwd, "fused flash attention backward (gfx950)",
         py::arg("dout"), py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("out"), py::arg("lse"), py::arg("bias"), py::arg("mask"),
         py::arg("bias_repeat"), py::arg("scale"), py::arg("need_dbias"),
         py::arg("q_repeat") = 1,
         py::arg("dq_out") = c10::nullopt, py::arg("dk_out") = c10::nullopt,
-        py::arg("dv_out") = c10::nullopt);
+        py::arg("dv_out") = c10::nullopt, py::arg("dropout_p") = 0.0,
+        py::arg("rng_state") = c10::nullopt);
 }

@@ -161,22 +161,61 @@ def hip_ff1_geglu(x, weight, bias=None):
     return _FF1GegluFn.apply(x, weight, bias)
 
 
+def _attn_fwd(ext, ctx, q, k, v, bias, mask, bias_repeat, scale,
+              dropout_p, rng_state, **kw):
+    """ext.attn_fwd with or without attention-probability dropout.
+    Returns (out, lse, rng_state); rng_state is the int64[2] device
+    tensor (seed, offset) the kernel used — the caller's, or the one the
+    forward drew from the default generator — and None without dropout.
+    It is kept on ctx for the backward (a plain attribute: it is neither
+    an input nor an output of the graph the Function records)."""
+    ctx.dropout_p = dropout_p
+    if dropout_p > 0.:
+        out, lse, rng_state = ext.attn_fwd(
+            q, k, v, bias, mask, bias_repeat, scale, dropout_p=dropout_p,
+            rng_state=rng_state, **kw)
+    else:
+        out, lse = ext.attn_fwd(q, k, v, bias, mask, bias_repeat, scale, **kw)
+        rng_state = None
+    ctx.rng_state = rng_state
+    return out, lse, rng_state
+
+
+def _drop_kw(ctx):
+    if ctx.dropout_p > 0.:
+        return dict(dropout_p=ctx.dropout_p, rng_state=ctx.rng_state)
+    return {}
+
+
+def _fn_result(ctx, out, rng_state, want_state):
+    """(out, rng_state) when the caller asked for the state, else out."""
+    if not want_state:
+        return out
+    assert rng_state is not None, "return_rng_state needs dropout_p > 0"
+    ctx.mark_non_differentiable(rng_state)
+    return out, rng_state
+
+
 class _AttentionFn(torch.autograd.Function):
     """Fused flash attention (bf16, head dim 64) with broadcast pair bias.
 
     bias has shape (B // bias_repeat, h, Lq, Lk); consecutive groups of
     `bias_repeat` batch entries share a bias slice (the axial-attention
-    fold — never materialized).
+    fold — never materialized).  dropout_p > 0 drops attention
+    probabilities inside the kernels (ops/hip/attn_dropout.h).
     """
 
     @staticmethod
-    def forward(ctx, q, k, v, bias, mask, bias_repeat, scale):
+    def forward(ctx, q, k, v, bias, mask, bias_repeat, scale,
+                dropout_p=0., rng_state=None, want_state=False):
         ext = _load_ext()
         # q/k/v are consumed through their strides (no permute copies);
         # only the innermost head-dim must be dense
         bias_c = bias.contiguous() if bias is not None else None
         mask_c = mask.contiguous() if mask is not None else None
-        out, lse = ext.attn_fwd(q, k, v, bias_c, mask_c, bias_repeat, scale)
+        out, lse, rng_state = _attn_fwd(ext, ctx, q, k, v, bias_c, mask_c,
+                                        bias_repeat, scale, dropout_p,
+                                        rng_state)
         ctx.save_for_backward(q, k, v, out, lse,
                               *( [bias_c] if bias_c is not None else [] ))
         ctx.has_bias = bias_c is not None
@@ -184,24 +223,30 @@ class _AttentionFn(torch.autograd.Function):
         ctx.bias_repeat = bias_repeat
         ctx.scale = scale
         ctx.bias_requires_grad = bias is not None and bias.requires_grad
-        return out
+        return _fn_result(ctx, out, rng_state, want_state)
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *_):
         ext = _load_ext()
         saved = ctx.saved_tensors
         q, k, v, out, lse = saved[:5]
         bias = saved[5] if ctx.has_bias else None
         need_dbias = ctx.bias_requires_grad
         rets = ext.attn_bwd(dout, q, k, v, out, lse, bias,
-                            ctx.mask, ctx.bias_repeat, ctx.scale, need_dbias)
+                            ctx.mask, ctx.bias_repeat, ctx.scale, need_dbias,
+                            **_drop_kw(ctx))
         dq, dk, dv = rets[:3]
         dbias = rets[3].to(bias.dtype) if need_dbias else None
-        return dq, dk, dv, dbias, None, None, None
+        return dq, dk, dv, dbias, None, None, None, None, None, None
 
 
 def hip_attention_core(q, k, v, bias=None, mask=None, context_mask=None,
-                       tie_dim=None, bias_repeat=1, scale=None):
+                       tie_dim=None, bias_repeat=1, scale=None,
+                       dropout_p=0., rng_state=None, return_rng_state=False):
+    """dropout_p > 0 drops attention probabilities in the kernels; the
+    mask is a function of `rng_state` (int64[2] device tensor: seed,
+    offset), drawn from the default generator when not given.
+    return_rng_state=True returns (out, rng_state)."""
     key_mask = context_mask if context_mask is not None else mask
     if key_mask is not None:
         key_mask = key_mask.to(torch.uint8)
@@ -221,12 +266,18 @@ def hip_attention_core(q, k, v, bias=None, mask=None, context_mask=None,
         q, k, v = (torch.nn.functional.pad(t, (0, pad)) for t in (q, k, v))
         out = hip_attention_core(q, k, v, bias=bias, mask=None,
                                  context_mask=key_mask, tie_dim=tie_dim,
-                                 bias_repeat=bias_repeat, scale=scale)
+                                 bias_repeat=bias_repeat, scale=scale,
+                                 dropout_p=dropout_p, rng_state=rng_state,
+                                 return_rng_state=return_rng_state)
+        if return_rng_state:
+            return out[0][..., :dh], out[1]
         return out[..., :dh]
     if tie_dim is not None:
         return _AttentionTiedFn.apply(q, k, v, bias, key_mask, tie_dim,
-                                      bias_repeat, scale)
-    return _AttentionFn.apply(q, k, v, bias, key_mask, bias_repeat, scale)
+                                      bias_repeat, scale, dropout_p,
+                                      rng_state, return_rng_state)
+    return _AttentionFn.apply(q, k, v, bias, key_mask, bias_repeat, scale,
+                              dropout_p, rng_state, return_rng_state)
 
 
 class _AttentionTiedFn(torch.autograd.Function):
@@ -242,7 +293,8 @@ class _AttentionTiedFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, q, k, v, bias, mask, tie_dim, bias_repeat, scale):
+    def forward(ctx, q, k, v, bias, mask, tie_dim, bias_repeat, scale,
+                dropout_p=0., rng_state=None, want_state=False):
         ext = _load_ext()
         Bh = q.shape[0]
         b = Bh // tie_dim
@@ -251,18 +303,21 @@ class _AttentionTiedFn(torch.autograd.Function):
         qm = q.reshape(b, tie_dim, *q.shape[1:]).mean(dim=1).contiguous()
         bias_c = bias.contiguous() if bias is not None else None
         mask_c = mask.contiguous() if mask is not None else None
-        out, lse = ext.attn_fwd(qm, k, v, bias_c, mask_c, bias_repeat,
-                                scale, q_repeat=tie_dim)
+        # the dropout mask is indexed by the K/V batch entry, so every
+        # member of a tie group draws its own (as the eager composition)
+        out, lse, rng_state = _attn_fwd(ext, ctx, qm, k, v, bias_c, mask_c,
+                                        bias_repeat, scale, dropout_p,
+                                        rng_state, q_repeat=tie_dim)
         ctx.save_for_backward(qm, k, v, out, lse,
                               *([bias_c] if bias_c is not None else []))
         ctx.has_bias = bias_c is not None
         ctx.mask = mask_c
         ctx.meta = (tie_dim, bias_repeat, scale)
         ctx.bias_requires_grad = bias is not None and bias.requires_grad
-        return out
+        return _fn_result(ctx, out, rng_state, want_state)
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *_):
         ext = _load_ext()
         saved = ctx.saved_tensors
         qm, k, v, out, lse = saved[:5]
@@ -271,7 +326,7 @@ class _AttentionTiedFn(torch.autograd.Function):
         need_dbias = ctx.bias_requires_grad
         rets = ext.attn_bwd(dout, qm, k, v, out, lse, bias,
                             ctx.mask, bias_repeat, scale, need_dbias,
-                            q_repeat=tie_dim)
+                            q_repeat=tie_dim, **_drop_kw(ctx))
         dq_exp, dk, dv = rets[:3]
         Bh = dq_exp.shape[0]
         b = Bh // tie_dim
@@ -280,7 +335,7 @@ class _AttentionTiedFn(torch.autograd.Function):
                    .expand(b, tie_dim, *dq_exp.shape[1:]) \
                    .reshape(Bh, *dq_exp.shape[1:])
         dbias = rets[3].to(bias.dtype) if need_dbias else None
-        return dq, dk, dv, dbias, None, None, None, None
+        return dq, dk, dv, dbias, None, None, None, None, None, None, None
 
 
 class _AttentionPackedFn(torch.autograd.Function):
@@ -291,7 +346,8 @@ class _AttentionPackedFn(torch.autograd.Function):
     ~5% of a training step)."""
 
     @staticmethod
-    def forward(ctx, packed, heads, inner, bias, mask, bias_repeat, scale):
+    def forward(ctx, packed, heads, inner, bias, mask, bias_repeat, scale,
+                dropout_p=0., rng_state=None, want_state=False):
         ext = _load_ext()
         B, L = packed.shape[0], packed.shape[1]
         dh = inner // heads
@@ -302,17 +358,19 @@ class _AttentionPackedFn(torch.autograd.Function):
         q, k, v = view(0), view(inner), view(2 * inner)
         bias_c = bias.contiguous() if bias is not None else None
         mask_c = mask.contiguous() if mask is not None else None
-        out, lse = ext.attn_fwd(q, k, v, bias_c, mask_c, bias_repeat, scale)
+        out, lse, rng_state = _attn_fwd(ext, ctx, q, k, v, bias_c, mask_c,
+                                        bias_repeat, scale, dropout_p,
+                                        rng_state)
         ctx.save_for_backward(packed, out, lse,
                               *([bias_c] if bias_c is not None else []))
         ctx.has_bias = bias_c is not None
         ctx.mask = mask_c
         ctx.meta = (heads, inner, bias_repeat, scale)
         ctx.bias_requires_grad = bias is not None and bias.requires_grad
-        return out
+        return _fn_result(ctx, out, rng_state, want_state)
 
     @staticmethod
-    def backward(ctx, dout):
+    def backward(ctx, dout, *_):
         ext = _load_ext()
         saved = ctx.saved_tensors
         packed, out, lse = saved[:3]
@@ -337,17 +395,21 @@ class _AttentionPackedFn(torch.autograd.Function):
         need_dbias = ctx.bias_requires_grad
         rets = ext.attn_bwd(dout, q, k, v, out, lse, bias, ctx.mask,
                             bias_repeat, scale, need_dbias,
-                            dq_out=dq, dk_out=dk, dv_out=dv)
+                            dq_out=dq, dk_out=dk, dv_out=dv,
+                            **_drop_kw(ctx))
         dbias = rets[3].to(bias.dtype) if need_dbias else None
-        return dpacked, None, None, dbias, None, None, None
+        return (dpacked, None, None, dbias, None, None, None, None, None,
+                None)
 
 
 def hip_attention_packed(packed, heads, inner, bias=None, mask=None,
-                         bias_repeat=1):
+                         bias_repeat=1, dropout_p=0., rng_state=None,
+                         return_rng_state=False):
     key_mask = mask.to(torch.uint8) if mask is not None else None
     scale = (inner // heads) ** -0.5
     return _AttentionPackedFn.apply(packed, heads, inner, bias, key_mask,
-                                    bias_repeat, scale)
+                                    bias_repeat, scale, dropout_p, rng_state,
+                                    return_rng_state)
 
 
 def _uniform_row_stride(t):

@@ -3,7 +3,15 @@ trunk's real shape classes (stable within-run numbers, independent of
 full-bench box noise).  Run on an MI355X:
 
     PYTHONPATH=/root/repo python tools/attn_bench.py
+
+`--dropout P` instead prints, per shape class and in the same run, the
+forward+backward time of the fused kernels without dropout, of the
+fused kernels with attention-probability dropout P, and of the eager
+dropout composition (ops/eager.py with the bias repeated), the latter
+on a batch cut to `--eager-batch` folded rows so that its (B, h, n, n)
+tensors fit, with its time scaled to the full batch.
 """
+import argparse
 import os
 import sys
 
@@ -39,9 +47,68 @@ def attn_shapes(b=5, n=256, m=128, h=8, d=64):
     ]
 
 
+def dropout_ab(ext, p, eager_batch):
+    """Within-run A/B of one training step of the attention core."""
+    from alphafold2_amd.ops import eager
+    h, d = 8, 64
+    scale = d ** -0.5
+    print(f"{'shape':8s} {'fused_ms':>9s} {'drop_ms':>9s} {'drop/fused':>10s} "
+          f"{'eager_ms':>9s} {'eager/drop':>10s}   (fwd+bwd, dropout={p}; "
+          f"eager measured at B={eager_batch} and scaled)")
+    for label, B, Lq, Lk, brep in attn_shapes():
+        mk = lambda *s: torch.randn(*s, device='cuda', dtype=torch.bfloat16)
+        q, k, v = mk(B, h, Lq, d), mk(B, h, Lk, d), mk(B, h, Lk, d)
+        bias = mk(B // brep, h, Lq, Lk) if brep else None
+        dout = mk(B, h, Lq, d)
+        r, need_db = brep or 1, bias is not None
+
+        def fused(pd):
+            kw = dict(dropout_p=pd) if pd > 0 else {}
+            res = ext.attn_fwd(q, k, v, bias, None, r, scale, **kw)
+            if pd > 0:
+                kw['rng_state'] = res[2]
+            ext.attn_bwd(dout, q, k, v, res[0], res[1], bias, None, r,
+                         scale, need_db, **kw)
+
+        t_plain = time_fn(lambda: fused(0.), iters=15)
+        t_drop = time_fn(lambda: fused(p), iters=15)
+
+        # eager composition on a reduced batch (whole bias-repeat groups)
+        Be = min(B, eager_batch)
+        re_ = min(r, Be)
+        Be = Be // re_ * re_
+        qe, ke, ve = (t[:Be].clone().requires_grad_(True) for t in (q, k, v))
+        be = bias[:max(1, Be // re_)].clone().requires_grad_(True) \
+            if brep else None
+        de = dout[:Be]
+
+        def eager_step():
+            b = be.repeat_interleave(re_, dim=0) if be is not None else None
+            out = eager.attention_core(qe, ke, ve, bias=b, dropout=p,
+                                       training=True)
+            out.backward(de)
+            for t in (qe, ke, ve, be):
+                if t is not None:
+                    t.grad = None
+
+        t_eager = time_fn(eager_step, iters=5, warmup=2) * (B / Be)
+        print(f"{label:8s} {t_plain:9.3f} {t_drop:9.3f} "
+              f"{t_drop / t_plain:10.2f} {t_eager:9.3f} "
+              f"{t_eager / t_drop:10.2f}")
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--dropout', type=float, default=0.,
+                    help='A/B the fused dropout kernels against the fused '
+                         'no-dropout kernels and the eager composition')
+    ap.add_argument('--eager-batch', type=int, default=128,
+                    help='folded batch rows the eager composition runs on')
+    args = ap.parse_args()
     ext = _load_ext()
     assert ext is not None
+    if args.dropout > 0.:
+        return dropout_ab(ext, args.dropout, args.eager_batch)
     h, d = 8, 64
     print(f"{'shape':8s} {'fwd_ms':>8s} {'fwd_TF':>7s} {'bwd_ms':>8s} {'bwd_TF':>7s}")
     for label, B, Lq, Lk, brep in attn_shapes():
