@@ -23,7 +23,11 @@
 //    layout for P·V.
 //  * Backward is FlashAttention-2 style: delta = rowsum(dO*O), a dQ
 //    kernel and a dK/dV kernel, each recomputing P from (Q,K,bias,lse).
-//    dBias is emitted with fp32 atomics folded over bias_repeat.
+//    With a bias gradient wanted, dK/dV instead stores its bf16 dS tile
+//    to a scratch; dQ = scale dS K streams that scratch and dBias is a
+//    one-writer sum of it over bias_repeat.  The older path (dBias by
+//    fp32 atomics, bounded by the chip's float-atomic rate) stays
+//    selectable with ds_scratch_bytes = 0.
 //
 // MFMA fragment conventions (verified on HW by tools/mfma_probe.hip):
 //  * C/D: col = lane&15, row = (lane>>4)*4 + reg   [guide §3, measured]
@@ -876,7 +880,27 @@ void attn_bwd_dq_kernel(TView q, TView k, TView v,
 //   S^T = K Q^T,  P^T,  dV += P^T dO,  dP^T = V dO^T,
 //   dS^T = P^T (dP^T - delta) scale,  dK += dS^T Q.
 
-template <bool HAS_BIAS, bool HAS_MASK, bool NEED_DBIAS, bool HAS_DROP>
+// dBias modes of the dK/dV kernel.  DBIAS_ATOMIC folds dS into the fp32
+// dbias with one atomic per element (plain stores at bias_repeat == 1);
+// DBIAS_STORE writes the bf16 dS^T tile to a [plane][kv][q] scratch that
+// attn_bwd_dq_from_ds_kernel and attn_dbias_sum_kernel consume.
+constexpr int DBIAS_NONE = 0;
+constexpr int DBIAS_ATOMIC = 1;
+constexpr int DBIAS_STORE = 2;
+
+// dS scratch: one [n_k * 64][n_q * 64] bf16 plane per (batch, head) of
+// the slice, kv-major.  The producer stores whole 64x64 tiles (zeros
+// where q >= Lq or kv >= Lk), so every element of a plane is written;
+// the consumers still read only rows kv < Lk and 16-byte chunks that
+// start at q < Lq.
+struct DsView {
+  bf16_t* p;
+  long plane;   // elements per (batch, head) plane
+  int pitch;    // elements per kv row (n_q * 64)
+  int bh0;      // batch * heads + head of the slice's first plane
+};
+
+template <bool HAS_BIAS, bool HAS_MASK, int DBIAS, bool HAS_DROP>
 __global__ __launch_bounds__(256, 2)
 void attn_bwd_dkv_kernel(TView q, TView k, TView v,
                          const bf16_t* __restrict__ bias,
@@ -886,7 +910,7 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
                          const float* __restrict__ delta,
                          TViewMut dk, TViewMut dv,
                          float* __restrict__ dbias,
-                         int dbias_chunks, long dbias_stride,
+                         int dbias_chunks, long dbias_stride, DsView ds,
                          int Lq, int Lk, int heads, int bias_repeat, int q_repeat,
                          float scale, BwdDrop<HAS_DROP> drop) {
   __shared__ char k_lds[BK * ROWB];
@@ -905,7 +929,7 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
   if constexpr (HAS_DROP) dpar = drop_params(drop, Lq, Lk);
 
   const int ktile = blockIdx.x;
-  const int bh = blockIdx.y;
+  const int bh = ds.bh0 + blockIdx.y;
   const int batch = bh / heads;
   const int head = bh - batch * heads;
   const int lane = threadIdx.x & 63;
@@ -922,12 +946,18 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
   const int bias_batch = batch / bias_repeat;
   if (HAS_BIAS)
     bias_g = bias + (long)(bias_batch * heads + head) * Lq * Lk;
-  if (NEED_DBIAS) {
+  if (DBIAS == DBIAS_ATOMIC) {
     // fold into one of `dbias_chunks` scratch copies: the repeat group
     // splits across chunks, cutting same-address atomic chain depth
     const int chunk = (batch % bias_repeat) % dbias_chunks;
     dbias_g = dbias + (long)chunk * dbias_stride
         + (long)(bias_batch * heads + head) * Lq * Lk;
+  }
+  // this wave's 16 kv rows of the (batch, head) dS plane
+  bf16_t* ds_g = nullptr;
+  if (DBIAS == DBIAS_STORE) {
+    ds_g = ds.p + (long)blockIdx.y * ds.plane
+        + (long)(ktile * BK + wave * 16) * ds.pitch;
   }
 
   const int kv_rows = min(BK, Lk - ktile * BK);
@@ -1110,7 +1140,24 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
     for (int kblk = 0; kblk < 2; ++kblk)
       dst_frag[kblk] = frag_row(sw, lane & 15, kblk);
 
-    if (NEED_DBIAS) {
+    if (DBIAS == DBIAS_STORE) {
+      // wave-local drain of the [16 kv][64 q] bf16 tile the dK MFMA
+      // reads: 128-byte rows, eight lanes per row, 16-byte stores.  The
+      // tile is this wave's own scratch, so no block barrier; rows and
+      // columns past Lk / Lq hold the zeros that P^T = 0 gave them.
+#pragma unroll
+      for (int pass = 0; pass < 2; ++pass) {
+        const int row = pass * 8 + (lane >> 3);
+        const int c16 = (lane & 7) << 4;
+        const float4 val =
+            *reinterpret_cast<const float4*>(sw + swz(row, c16));
+        *reinterpret_cast<float4*>(
+            reinterpret_cast<char*>(ds_g + (long)row * ds.pitch + t * BQ)
+            + c16) = val;
+      }
+    }
+
+    if (DBIAS == DBIAS_ATOMIC) {
       // cooperative transposed drain of the 64x64 dS tile from the four
       // per-wave scratches into dbias.  Lanes map to CONTIGUOUS kv
       // addresses so each store/atomic instruction coalesces; when
@@ -1159,6 +1206,209 @@ void attn_bwd_dkv_kernel(TView q, TView k, TView v,
         dv_g[(long)row * dv.rs + c * 16 + (lane & 15)] =
             (bf16_t)dv_acc[c][reg];
       }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// backward dQ from stored dS: dQ[b,h] = scale * dS[b,h] K[b,h].  The
+// dK/dV kernel (DBIAS_STORE) has left the unscaled bf16 dS^T, dropout
+// and masks applied, in the scratch; this kernel streams it once and
+// knows nothing of bias, mask, lse, delta, dropout, Q, V or dO.  One
+// block per (64 q rows, batch*head), loop over kv tiles.  Both operands
+// arrive kv-major while the MFMA wants the kv reduction axis
+// lane-contiguous: the tiles go to LDS as they are (16-byte writes) and
+// the fragments come back through gfx950's transposing LDS read, so no
+// 2-byte transposition stores.  LDS tiles are double buffered: one
+// barrier per kv tile.
+
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef short s16x8 __attribute__((ext_vector_type(8)));
+
+// 8-element MFMA operand (k = (lane>>4)*8 + j, as frag_row) whose k axis
+// is the ROW axis of a swizzled row-major [64][64] bf16 LDS tile: lane
+// (i = lane&15) gets column col0 + i of rows kblk*32 + (lane>>4)*8 + j.
+// ds_read_b64_tr_b16 serves a 16-lane group one 4-row x 16-column block:
+// lane 4a+p gives the address of row a, columns 4p..4p+3, and receives
+// column (lane&15) of the 4 rows; two reads cover j = 0..3 and 4..7.
+// The 16-byte swizzle keeps each 8-byte piece whole.  EXEC must be full.
+__device__ __forceinline__ bf16x8 frag_tr(const char* lds, int col0,
+                                          int kblk) {
+  typedef __attribute__((address_space(3))) s16x4* lds_ptr;
+  const int lane = threadIdx.x & 63;
+  const int i = lane & 15;
+  const int row = kblk * 32 + ((lane >> 4) << 3) + (i >> 2);
+  const int colb = (col0 + ((i & 3) << 2)) * (int)sizeof(bf16_t);
+  const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_ptr)(lds + swz(row, colb)));
+  const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (lds_ptr)(lds + swz(row + 4, colb)));
+  return __builtin_bit_cast(
+      bf16x8, (s16x8)__builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// stage_load with a column bound: chunks starting at col >= cols are 0
+__device__ __forceinline__ void stage_load_rc(const bf16_t* __restrict__ g,
+                                              long row_stride, int rows,
+                                              int cols, StageRegs& r) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    int idx = tid + pass * 256;
+    int row = idx >> 3;
+    int c8 = (idx & 7) << 3;
+    float4 val = {0, 0, 0, 0};
+    if (row < rows && c8 < cols) {
+      val = *reinterpret_cast<const float4*>(g + row * row_stride + c8);
+    }
+    (pass ? r.v1 : r.v0) = val;
+  }
+}
+
+__global__ __launch_bounds__(256)
+void attn_bwd_dq_from_ds_kernel(DsView ds, TView k, TViewMut dq,
+                                int Lq, int Lk, int heads, float scale) {
+  __shared__ __attribute__((aligned(16))) char ds_lds[2][BK * ROWB];  // [kv][q]
+  __shared__ __attribute__((aligned(16))) char k_lds[2][BK * ROWB];   // [kv][d]
+
+  const int qtile = blockIdx.x;
+  const int bh = ds.bh0 + blockIdx.y;
+  const int batch = bh / heads;
+  const int head = bh - batch * heads;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+
+  const bf16_t* ds_g = ds.p + (long)blockIdx.y * ds.plane + qtile * BQ;
+  const bf16_t* k_g = k.base(batch, head);
+  const int q_rows = min(BQ, Lq - qtile * BQ);
+
+  f32x4 dq_acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) dq_acc[c] = f32x4{0, 0, 0, 0};
+
+  const int n_kv = (Lk + BK - 1) / BK;
+  StageRegs dsreg, kreg;
+  stage_load_rc(ds_g, ds.pitch, min(BK, Lk), q_rows, dsreg);
+  stage_load(k_g, k.rs, min(BK, Lk), kreg);
+  for (int t = 0; t < n_kv; ++t) {
+    char* dsl = ds_lds[t & 1];
+    char* kl = k_lds[t & 1];
+    stage_store(dsreg, dsl);
+    stage_store(kreg, kl);
+    // the buffer written here was last read two tiles ago, before the
+    // barrier of the previous iteration
+    __syncthreads();
+    if (t + 1 < n_kv) {
+      const int next_rows = min(BK, Lk - (t + 1) * BK);
+      stage_load_rc(ds_g + (long)(t + 1) * BK * ds.pitch, ds.pitch,
+                    next_rows, q_rows, dsreg);
+      stage_load(k_g + (long)(t + 1) * BK * k.rs, k.rs, next_rows, kreg);
+    }
+
+    bf16x8 ds_frag[2];
+#pragma unroll
+    for (int kblk = 0; kblk < 2; ++kblk)
+      ds_frag[kblk] = frag_tr(dsl, wave * 16, kblk);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      f32x4 acc = dq_acc[c];
+#pragma unroll
+      for (int kblk = 0; kblk < 2; ++kblk) {
+        bf16x8 kf = frag_tr(kl, c * 16, kblk);
+        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ds_frag[kblk], kf, acc,
+                                                      0, 0, 0);
+      }
+      dq_acc[c] = acc;
+    }
+  }
+
+  bf16_t* dq_g = dq.base(batch, head) + (long)qtile * BQ * dq.rs;
+#pragma unroll
+  for (int reg = 0; reg < 4; ++reg) {
+    const int row = wave * 16 + (lane >> 4) * 4 + reg;
+    if (row < q_rows) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        dq_g[(long)row * dq.rs + c * 16 + (lane & 15)] =
+            (bf16_t)(dq_acc[c][reg] * scale);
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// dBias from stored dS: dbias[g,h,q,kv] = sum over the batch entries b of
+// repeat group g that lie in the slice [b0, b1) of dS[b,h,q,kv].  One
+// block per (group, head, 64x64 tile): fp32 accumulation in registers in
+// the scratch's kv-major layout, then one transposition through LDS and
+// plain stores — a single writer per element, so the result does not
+// depend on scheduling.  A group whose first entry lies before b0 was
+// started by an earlier slice and is added to when `accumulate` is set.
+
+__global__ __launch_bounds__(256)
+void attn_dbias_sum_kernel(DsView ds, float* __restrict__ dbias,
+                           int Lq, int Lk, int heads, int bias_repeat,
+                           int b0, int b1, int g0, int accumulate) {
+  __shared__ float tile[BQ][BK + 1];  // [q][kv], padded against conflicts
+
+  const int n_k = (Lk + BK - 1) / BK;
+  const int qtile = blockIdx.x / n_k;
+  const int ktile = blockIdx.x - qtile * n_k;
+  const int g = g0 + blockIdx.y / heads;
+  const int head = blockIdx.y % heads;
+  const int q_cols = min(BQ, Lq - qtile * BQ);
+  const int kv_rows = min(BK, Lk - ktile * BK);
+  const int r_lo = max(g * bias_repeat, b0);
+  const int r_hi = min((g + 1) * bias_repeat, b1);
+
+  // thread -> two 16-byte chunks of the [kv][q] tile, as stage_load
+  float acc[2][8];
+  const bf16_t* src[2];
+  bool ok[2];
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int idx = threadIdx.x + pass * 256;
+    const int row = idx >> 3;
+    const int c8 = (idx & 7) << 3;
+    ok[pass] = row < kv_rows && c8 < q_cols;
+    src[pass] = ds.p + ((long)(r_lo - b0) * heads + head) * ds.plane
+        + (long)(ktile * BK + row) * ds.pitch + qtile * BQ + c8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[pass][j] = 0.f;
+  }
+  const long step = (long)heads * ds.plane;
+#pragma unroll 4
+  for (int b = r_lo; b < r_hi; ++b) {
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      if (ok[pass]) {
+        const bf16x8 val = *reinterpret_cast<const bf16x8*>(src[pass]);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[pass][j] += to_f32(val[j]);
+      }
+      src[pass] += step;
+    }
+  }
+
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int idx = threadIdx.x + pass * 256;
+    const int row = idx >> 3;
+    const int c8 = (idx & 7) << 3;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) tile[c8 + j][row] = acc[pass][j];
+  }
+  __syncthreads();
+
+  const bool add = accumulate && g * bias_repeat < b0;
+  float* out = dbias + ((long)(g * heads + head) * Lq + (long)qtile * BQ) * Lk
+      + (long)ktile * BK;
+  const int kvc = threadIdx.x & 63;
+  for (int qq = threadIdx.x >> 6; qq < q_cols; qq += NWAVES) {
+    if (kvc < kv_rows) {
+      float* addr = out + (long)qq * Lk + kvc;
+      const float val = tile[qq][kvc];
+      *addr = add ? *addr + val : val;
     }
   }
 }
@@ -1758,7 +2008,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  c10::optional<at::Tensor> dk_out,
                                  c10::optional<at::Tensor> dv_out,
                                  double dropout_p,
-                                 c10::optional<at::Tensor> rng_state) {
+                                 c10::optional<at::Tensor> rng_state,
+                                 c10::optional<int64_t> ds_scratch_bytes) {
   check_qkv_bias(q, k, v, bias, bias_repeat, q_repeat, "attn_bwd");
   const bool has_drop = dropout_p != 0.0;
   BwdDrop<true> dr{};
@@ -1819,7 +2070,54 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   // zeros+sum traffic measured NET-NEGATIVE (tri bwd 4.0 -> 4.3 ms at
   // chunks=8, tools/attn_bench.py) — keep a single copy
   int dbias_chunks = 1;
-  if (need_dbias) {
+
+  // split dV/dK passes (4/3 waves per SIMD, but prefetch-free and
+  // +40% flops): measured SLOWER end-to-end than the combined kernel
+  // (748 vs 699 ms/step, r02) — combined stays default;
+  // AF2AMD_SPLIT_DKV=1 re-enables for tuning.
+  static const bool split_dkv = [] {
+    const char* e = getenv("AF2AMD_SPLIT_DKV");
+    return e != nullptr && e[0] == '1';
+  }();
+
+  // dS scratch path (docs/KERNELS.md "Attention backward: stored dS"):
+  // with a bias gradient wanted, the dK/dV kernel stores its bf16 dS
+  // tile instead of adding it to dbias with float atomics, dQ is a
+  // plain dS K product over that scratch and dbias a one-writer sum.
+  // The scratch is capped in bytes — a memory budget, not a tuned
+  // optimum; above the cap the three kernels run over consecutive batch
+  // slices that reuse one scratch.  0 selects the atomic path.
+  static const int64_t ds_scratch_default = [] {
+    const char* e = getenv("AF2AMD_DS_SCRATCH_BYTES");
+    if (e == nullptr || e[0] == '\0') return (int64_t)2 << 30;
+    char* end = nullptr;
+    const long long val = strtoll(e, &end, 10);
+    TORCH_CHECK(end != e && *end == '\0' && val >= 0,
+                "AF2AMD_DS_SCRATCH_BYTES must be a non-negative byte count, "
+                "got '", e, "'");
+    return (int64_t)val;
+  }();
+  const int64_t ds_cap = ds_scratch_bytes.value_or(ds_scratch_default);
+  TORCH_CHECK(ds_cap >= 0, "attn_bwd: ds_scratch_bytes must be >= 0, got ",
+              ds_cap);
+  const bool use_ds = need_dbias && ds_cap > 0 && !split_dkv;
+
+  const int n_q = (Lq + BQ - 1) / BQ, n_k = (Lk + BK - 1) / BK;
+  const long ds_plane = (long)n_q * BQ * n_k * BK;  // padded to whole tiles
+  int ds_slice = 0;  // batch entries per slice
+  at::Tensor ds_buf;
+  if (use_ds) {
+    const int64_t per_entry = (int64_t)H * ds_plane * sizeof(bf16_t);
+    ds_slice = (int)std::min<int64_t>(
+        B, std::max<int64_t>(1, ds_cap / per_entry));
+    TORCH_CHECK((long)n_q * BQ <= INT_MAX, "attn_bwd: Lq too large");
+    ds_buf = at::empty({(long)ds_slice * H * ds_plane}, q.options());
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(ds_buf.data_ptr()) % 16 == 0,
+                "attn_bwd: dS scratch must be 16-byte aligned");
+    // one writer per element: no zero fill, no chunk dimension to fold
+    dbias = at::empty({B / bias_repeat, H, Lq, Lk},
+                      q.options().dtype(at::kFloat));
+  } else if (need_dbias) {
     dbias = at::zeros({dbias_chunks, B / bias_repeat, H, Lq, Lk},
                       q.options().dtype(at::kFloat));
   }
@@ -1863,13 +2161,23 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
       dov, lse.data_ptr<float>(), delta.data_ptr<float>(), dqv,               \
       Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale, DROP)
 
-  if (has_bias && has_mask) { DISPATCH_DQ(true, true); }
-  else if (has_bias) { DISPATCH_DQ(true, false); }
-  else if (has_mask) { DISPATCH_DQ(false, true); }
-  else { DISPATCH_DQ(false, false); }
+  // the stored-dS path forms dQ after dK/dV, from the scratch
+  if (!use_ds) {
+    if (has_bias && has_mask) { DISPATCH_DQ(true, true); }
+    else if (has_bias) { DISPATCH_DQ(true, false); }
+    else if (has_mask) { DISPATCH_DQ(false, true); }
+    else { DISPATCH_DQ(false, false); }
+  }
 #undef DISPATCH_DQ
 #undef DISPATCH_DQ_
 
+  auto check_launch = [](const char* name) {
+    const hipError_t err = hipGetLastError();
+    TORCH_CHECK(err == hipSuccess, "attn_bwd: ", name, " launch failed: ",
+                hipGetErrorString(err));
+  };
+
+  DsView dsv{nullptr, 0, 0, 0};
 #define DISPATCH_DKV(HB, HM, DB)                                              \
   if (has_drop) DISPATCH_DKV_(HB, HM, DB, true, dr);                          \
   else DISPATCH_DKV_(HB, HM, DB, false, nd)
@@ -1879,9 +2187,37 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
       has_bias ? reinterpret_cast<const bf16_t*>(bias_c.data_ptr()) : nullptr,\
       has_mask ? mask_u8.data_ptr<unsigned char>() : nullptr,                 \
       dov, lse.data_ptr<float>(), delta.data_ptr<float>(), dkv, dvv,          \
-      DB ? dbias.data_ptr<float>() : nullptr,                                 \
-      dbias_chunks, need_dbias ? dbias.stride(0) : 0L,                        \
+      DB == DBIAS_ATOMIC ? dbias.data_ptr<float>() : nullptr,                 \
+      dbias_chunks, DB == DBIAS_ATOMIC ? dbias.stride(0) : 0L, dsv,           \
       Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale, DROP)
+
+  if (use_ds) {
+    // delta -> per slice: dK/dV (stores dS) -> dQ from dS -> dBias sum,
+    // all on one stream, so a slice's scratch is consumed before the
+    // next slice overwrites it.  Slices need not align to repeat groups:
+    // the sum adds to groups an earlier slice started.
+    const int R = (int)bias_repeat;
+    for (int b0 = 0; b0 < B; b0 += ds_slice) {
+      const int b1 = std::min(B, b0 + ds_slice);
+      dsv = DsView{reinterpret_cast<bf16_t*>(ds_buf.data_ptr()), ds_plane,
+                   n_q * BQ, b0 * H};
+      grid_k = dim3(n_k, (b1 - b0) * H);
+      if (has_mask) { DISPATCH_DKV(true, true, DBIAS_STORE); }
+      else { DISPATCH_DKV(true, false, DBIAS_STORE); }
+      check_launch("attn_bwd_dkv_kernel");
+      hipLaunchKernelGGL(attn_bwd_dq_from_ds_kernel,
+                         dim3(n_q, (b1 - b0) * H), dim3(256), 0, stream, dsv,
+                         kvv, dqv, Lq, Lk, H, (float)scale);
+      check_launch("attn_bwd_dq_from_ds_kernel");
+      const int g0 = b0 / R, g1 = (b1 - 1) / R;
+      hipLaunchKernelGGL(attn_dbias_sum_kernel,
+                         dim3(n_q * n_k, (g1 - g0 + 1) * H), dim3(256), 0,
+                         stream, dsv, dbias.data_ptr<float>(), Lq, Lk, H, R,
+                         b0, b1, g0, b0 > 0 ? 1 : 0);
+      check_launch("attn_dbias_sum_kernel");
+    }
+    return {dq, dk, dv, dbias};
+  }
 
 #define DISPATCH_DV(HB, HM)                                                   \
   hipLaunchKernelGGL((attn_bwd_dv_kernel<HB, HM>), grid_k, dim3(256), 0,      \
@@ -1901,15 +2237,6 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
       dbias_chunks, need_dbias ? dbias.stride(0) : 0L,                        \
       Lq, Lk, H, (int)bias_repeat, (int)q_repeat, (float)scale)
 
-  // split dV/dK passes (4/3 waves per SIMD, but prefetch-free and
-  // +40% flops): measured SLOWER end-to-end than the combined kernel
-  // (748 vs 699 ms/step, r02) — combined stays default;
-  // AF2AMD_SPLIT_DKV=1 re-enables for tuning.
-  static const bool split_dkv = [] {
-    const char* e = getenv("AF2AMD_SPLIT_DKV");
-    return e != nullptr && e[0] == '1';
-  }();
-
   // the split kernels do not know dropout: with it, always combined
   if (split_dkv && !has_drop) {
     if (has_bias && has_mask) DISPATCH_DV(true, true);
@@ -1925,12 +2252,12 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     else DISPATCH_DK(false, false, false);
   } else {
     if (need_dbias) {
-      if (has_mask) { DISPATCH_DKV(true, true, true); }
-      else { DISPATCH_DKV(true, false, true); }
-    } else if (has_bias && has_mask) { DISPATCH_DKV(true, true, false); }
-    else if (has_bias) { DISPATCH_DKV(true, false, false); }
-    else if (has_mask) { DISPATCH_DKV(false, true, false); }
-    else { DISPATCH_DKV(false, false, false); }
+      if (has_mask) { DISPATCH_DKV(true, true, DBIAS_ATOMIC); }
+      else { DISPATCH_DKV(true, false, DBIAS_ATOMIC); }
+    } else if (has_bias && has_mask) { DISPATCH_DKV(true, true, DBIAS_NONE); }
+    else if (has_bias) { DISPATCH_DKV(true, false, DBIAS_NONE); }
+    else if (has_mask) { DISPATCH_DKV(false, true, DBIAS_NONE); }
+    else { DISPATCH_DKV(false, false, DBIAS_NONE); }
   }
 #undef DISPATCH_DKV
 #undef DISPATCH_DKV_

@@ -64,7 +64,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  c10::optional<at::Tensor> dk_out,
                                  c10::optional<at::Tensor> dv_out,
                                  double dropout_p,
-                                 c10::optional<at::Tensor> rng_state);
+                                 c10::optional<at::Tensor> rng_state,
+                                 c10::optional<int64_t> ds_scratch_bytes);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd, "fused LayerNorm forward (gfx950)");
@@ -138,5 +139,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q_repeat") = 1,
         py::arg("dq_out") = c10::nullopt, py::arg("dk_out") = c10::nullopt,
         py::arg("dv_out") = c10::nullopt, py::arg("dropout_p") = 0.0,
-        py::arg("rng_state") = c10::nullopt);
+        py::arg("rng_state") = c10::nullopt,
+        // byte cap of the stored-dS scratch; None = AF2AMD_DS_SCRATCH_BYTES
+        // (default 2 GiB), 0 = the float-atomic dBias path
+        py::arg("ds_scratch_bytes") = c10::nullopt);
 }

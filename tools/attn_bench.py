@@ -2,7 +2,7 @@
 trunk's real shape classes (stable within-run numbers, independent of
 full-bench box noise).  Run on an MI355X:
 
-    PYTHONPATH=/root/repo python tools/attn_bench.py
+    python tools/attn_bench.py
 
 `--dropout P` instead prints, per shape class and in the same run, the
 forward+backward time of the fused kernels without dropout, of the
@@ -10,6 +10,14 @@ fused kernels with attention-probability dropout P, and of the eager
 dropout composition (ops/eager.py with the bias repeated), the latter
 on a batch cut to `--eager-batch` folded rows so that its (B, h, n, n)
 tensors fit, with its time scaled to the full batch.
+
+`--ds-ab` times the attention backward, in one process and alternating,
+through the float-atomic dBias path (`ds_scratch_bytes=0`) and through
+the stored-dS path, at the batch-5 trunk shapes (MSA row, both
+triangles, MSA column, and one bias_repeat = 1 shape), and splits each
+backward into its kernels (delta, dK/dV, dQ, dBias sum, fills) with
+torch.profiler.  The MSA column has no bias and runs the same kernels
+on both settings: its two figures show the noise of the comparison.
 """
 import argparse
 import os
@@ -97,6 +105,76 @@ def dropout_ab(ext, p, eager_batch):
               f"{t_eager / t_drop:10.2f}")
 
 
+def _kernel_ms(fn, iters=5):
+    """{kernel family: ms per call} of fn from torch.profiler."""
+    from torch.profiler import ProfilerActivity, profile
+    fams = [('dkv', 'attn_bwd_dkv_kernel'),
+            ('dq', 'attn_bwd_dq_from_ds_kernel'),
+            ('dq', 'attn_bwd_dq_kernel'), ('sum', 'attn_dbias_sum_kernel'),
+            ('delta', 'attn_delta_kernel')]
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        for _ in range(iters):
+            fn()
+        torch.cuda.synchronize()
+    out = {}
+    for ev in prof.key_averages():
+        t = getattr(ev, 'device_time_total', None)
+        if t is None:
+            t = ev.cuda_time_total
+        if t <= 0:
+            continue
+        fam = next((f for f, n in fams if n in ev.key), 'other')
+        out[fam] = out.get(fam, 0.) + t / 1e3 / iters
+    return out
+
+
+def ds_ab(ext, rounds, iters):
+    """Within-run A/B of the attention backward: float-atomic dBias
+    against the stored-dS path, alternating `rounds` times."""
+    h, d = 8, 64
+    scale = d ** -0.5
+    shapes = attn_shapes() + [("bias_r1", 64, 256, 256, 1)]
+    print(f"{'shape':8s} {'path':7s} {'bwd_ms':>8s} {'min':>8s} {'max':>8s} "
+          f"{'TF':>6s}   kernels (ms per call, torch.profiler)")
+    for label, B, Lq, Lk, brep in shapes:
+        mk = lambda *s: torch.randn(*s, device='cuda', dtype=torch.bfloat16)
+        q, k, v = mk(B, h, Lq, d), mk(B, h, Lk, d), mk(B, h, Lk, d)
+        bias = mk(B // brep, h, Lq, Lk) if brep else None
+        dout = mk(B, h, Lq, d)
+        r, need_db = brep or 1, bias is not None
+        out, lse = ext.attn_fwd(q, k, v, bias, None, r, scale)
+        paths = {
+            'atomic': lambda: ext.attn_bwd(dout, q, k, v, out, lse, bias,
+                                           None, r, scale, need_db,
+                                           ds_scratch_bytes=0),
+            'ds': lambda: ext.attn_bwd(dout, q, k, v, out, lse, bias, None,
+                                       r, scale, need_db,
+                                       ds_scratch_bytes=2 << 30),
+        }
+        times = {name: [] for name in paths}
+        for _ in range(rounds):
+            for name, fn in paths.items():
+                times[name].append(time_fn(fn, iters=iters, warmup=2))
+        gb = 10e-12 * B * h * Lq * Lk * d
+        for name, fn in paths.items():
+            ts = sorted(times[name])
+            med = ts[len(ts) // 2]
+            try:
+                km = _kernel_ms(fn)
+            except Exception as exc:  # the breakdown is extra: say why
+                km = {'profiler failed': repr(exc)}
+            extra = ''
+            if name == 'ds' and need_db and 'dq' in km:
+                gbytes = B * h * (Lq * Lk + Lk * d + Lq * d) * 2 / 1e9
+                extra = f"  dq_stream={gbytes / (km['dq'] / 1e3):.0f} GB/s"
+            ks = ' '.join(f"{f}={t:.3f}" if isinstance(t, float)
+                          else f"{f}: {t}" for f, t in sorted(km.items()))
+            print(f"{label:8s} {name:7s} {med:8.3f} {ts[0]:8.3f} "
+                  f"{ts[-1]:8.3f} {gb / (med / 1e3):6.1f}   {ks}{extra}",
+                  flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--dropout', type=float, default=0.,
@@ -104,9 +182,18 @@ def main():
                          'no-dropout kernels and the eager composition')
     ap.add_argument('--eager-batch', type=int, default=128,
                     help='folded batch rows the eager composition runs on')
+    ap.add_argument('--ds-ab', action='store_true',
+                    help='A/B the backward: float-atomic dBias against the '
+                         'stored-dS path, alternating in one process')
+    ap.add_argument('--rounds', type=int, default=3,
+                    help='--ds-ab: alternations per shape')
+    ap.add_argument('--iters', type=int, default=10,
+                    help='--ds-ab: timed calls per alternation')
     args = ap.parse_args()
     ext = _load_ext()
     assert ext is not None
+    if args.ds_ab:
+        return ds_ab(ext, args.rounds, args.iters)
     if args.dropout > 0.:
         return dropout_ab(ext, args.dropout, args.eager_batch)
     h, d = 8, 64
