@@ -106,7 +106,40 @@ class SE3RefinerLayer(nn.Module):
         self.ff = nn.Sequential(
             nn.Linear(dim, dim * 2), nn.SiLU(), nn.Linear(dim * 2, dim))
 
+    def _fused_forward(self, h, x, edges, mask):
+        """Fused fp32 attention core (K15), training and inference: one
+        kernel for the pair-bias Linear, the distance term, the masked
+        softmax and both aggregations, two for the backward
+        (ops/hip/se3core.hip).  The norm, the projections, `to_out`,
+        `coors_head`, the coordinate update and the feed-forward stay in
+        Python autograd.  Returns None when `dispatch.se3_core_fusable`
+        rejects the configuration (the caller then runs the eager
+        composition)."""
+        from ..ops import dispatch as _dispatch
+        inner = self.to_q.out_features
+        if not _dispatch.se3_core_fusable(
+                h, edges, heads=self.heads, dim_head=inner // self.heads):
+            return None
+        from ..ops import hip_autograd
+        b, n, _ = h.shape
+        hh = self.norm(h)
+        if mask is not None:
+            mask = mask.bool().expand(b, n)
+        out, dxh = hip_autograd.hip_se3_core(
+            self.to_q(hh), self.to_k(hh), self.to_v(hh), x, edges,
+            self.edge_bias.weight, self.edge_bias.bias, self.scale,
+            self.eps, mask)
+        h = h + self.to_out(out)
+        cw = self.coors_head(hh)                             # (b, n, H)
+        x = x + (dxh * cw.unsqueeze(-1)).sum(dim=2)
+        h = h + self.ff(self.norm(h))
+        return h, x
+
     def forward(self, h, x, edges=None, mask=None):
+        fused = self._fused_forward(h, x, edges, mask)
+        if fused is not None:
+            return fused
+
         b, n, _ = h.shape
         hh = self.norm(h)
 

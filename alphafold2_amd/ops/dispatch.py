@@ -305,6 +305,59 @@ def ipa_core_fusable(x, pairwise_repr, *, heads, scalar_key_dim,
     return False
 
 
+def _se3_fused_enabled():
+    # read per call so an A/B measurement can flip it inside one process
+    return os.environ.get("AF2AMD_SE3_FUSED", "1") != "0"
+
+
+def se3_core_fusable(h, edges, *, heads, dim_head):
+    """Gate of the fused SE(3) refiner attention core (K15, forward and
+    backward).  True when `hip_autograd.hip_se3_core` covers the
+    configuration; otherwise the caller runs the eager composition and,
+    on a GPU with the extension loaded, the failed predicate is named in
+    a fallback warning.  AF2AMD_SE3_FUSED=0 turns the fused path off
+    without a warning (A/B measurement).  Looks at shapes and host-side
+    properties only: no device sync, so the gate is safe inside hipGraph
+    capture.  It must not look at the capture state either: a step whose
+    warmup ran the fused core and whose capture ran the eager
+    composition would issue that composition's GEMMs for the first time
+    under capture, which hipBLASLt refuses ('operation not permitted
+    when stream is capturing') and which ends the process."""
+    if not _se3_fused_enabled() or not _want_hip(h):
+        return False
+    ext = _load_ext()
+    n = h.shape[1]
+    edge_dim = edges.shape[-1] if edges is not None else 0
+    autocast = torch.is_autocast_enabled('cuda')
+    if not hasattr(ext, 'se3_core_bwd'):
+        reason = 'extension built without se3_core_bwd'
+    elif edges is None:
+        reason = 'edges=None'
+    elif not 1 <= heads <= 8:
+        reason = f'heads={heads} (fused kernel covers 1 to 8)'
+    elif dim_head % 4 != 0 or not 4 <= dim_head <= 64:
+        reason = (f'dim_head={dim_head} (fused kernel covers multiples '
+                  'of 4 up to 64)')
+    elif edge_dim % 64 != 0 or not 64 <= edge_dim <= 512:
+        reason = (f'edge dim {edge_dim} (fused kernel covers multiples '
+                  'of 64 up to 512)')
+    elif h.dtype == torch.float64:
+        reason = 'dtype=torch.float64 (fused kernel is fp32)'
+    elif not autocast and (h.dtype != torch.float32
+                           or edges.dtype != torch.float32):
+        # under autocast custom_fwd casts every operand to fp32
+        reason = (f'dtype={h.dtype} / edges {edges.dtype} outside autocast '
+                  '(fused kernel is fp32)')
+    elif n > ext.se3_core_max_n(heads, dim_head, edge_dim):
+        reason = (f'n={n} exceeds the LDS bound '
+                  f'{ext.se3_core_max_n(heads, dim_head, edge_dim)} for '
+                  f'heads={heads}')
+    else:
+        return True
+    warn_gpu_fallback('se3_core', reason)
+    return False
+
+
 def layer_norm(x, weight, bias, eps=1e-5):
     if using_hip(x, 'layernorm_fwd'):
         from .hip_autograd import hip_layer_norm

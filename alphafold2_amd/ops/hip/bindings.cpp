@@ -44,6 +44,16 @@ std::vector<at::Tensor> ipa_core_bwd(
     double scale_p, double eps, c10::optional<at::Tensor> mask,
     bool need_dpair, bool need_drot);
 long ipa_core_max_n(long heads, long pair_dim);
+std::vector<at::Tensor> se3_core_fwd(
+    at::Tensor q, at::Tensor k, at::Tensor v, at::Tensor x,
+    at::Tensor edges, at::Tensor w_e, at::Tensor b_e, double scale,
+    double eps, c10::optional<at::Tensor> mask, bool save_attn);
+std::vector<at::Tensor> se3_core_bwd(
+    at::Tensor dout, at::Tensor ddxh, at::Tensor attn, at::Tensor q,
+    at::Tensor k, at::Tensor v, at::Tensor x, at::Tensor edges,
+    at::Tensor w_e, at::Tensor b_e, double scale, double eps,
+    c10::optional<at::Tensor> mask, bool need_dedges);
+long se3_core_max_n(long heads, long dim_head, long edge_dim);
 at::Tensor pairrep_fwd(at::Tensor left, at::Tensor right, at::Tensor emb,
                        at::Tensor rel);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -120,6 +130,26 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "largest sequence length whose IPA core forward and backward fit "
         "the device's LDS per block",
         py::arg("heads"), py::arg("pair_dim") = 512);
+  m.def("se3_core_fwd", &se3_core_fwd,
+        "fused fp32 SE(3) refiner attention core forward -> [out, dxh, "
+        "attn]; attn is saved for the backward only with save_attn "
+        "(gfx950, K15)",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("x"),
+        py::arg("edges"), py::arg("w_e"), py::arg("b_e"), py::arg("scale"),
+        py::arg("eps"), py::arg("mask") = c10::nullopt,
+        py::arg("save_attn") = false);
+  m.def("se3_core_bwd", &se3_core_bwd,
+        "fused fp32 SE(3) refiner attention core backward: gradients of "
+        "the seven core inputs, row-side + column-side kernels, no atomics "
+        "(gfx950, K15)",
+        py::arg("dout"), py::arg("ddxh"), py::arg("attn"), py::arg("q"),
+        py::arg("k"), py::arg("v"), py::arg("x"), py::arg("edges"),
+        py::arg("w_e"), py::arg("b_e"), py::arg("scale"), py::arg("eps"),
+        py::arg("mask") = c10::nullopt, py::arg("need_dedges") = true);
+  m.def("se3_core_max_n", &se3_core_max_n,
+        "largest sequence length whose SE(3) core forward and backward "
+        "fit the device's LDS per block",
+        py::arg("heads"), py::arg("dim_head"), py::arg("edge_dim"));
   m.def("wgrad", &wgrad,
         "split-K weight-gradient GEMM dY^T @ X (gfx950 MFMA, fp32 out)",
         py::arg("dY"), py::arg("X"));

@@ -683,6 +683,64 @@ def hip_ipa_core(q_s, k_s, v_s, q_pg, k_pg, v_pg, bias, pair, rot, trans,
                              float(eps)))
 
 
+def _dense16(t):
+    """Contiguous and 16-byte aligned (the kernels read float4): a
+    contiguous view at an odd offset of its storage is copied."""
+    t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+class _SE3CoreFn(torch.autograd.Function):
+    """Fused fp32 SE(3) refiner attention core (K15): qk + in-kernel pair
+    bias Linear + distance term + key-masked softmax + value and
+    displacement aggregation in one kernel.  When a gradient is required
+    the forward also saves the probabilities (b,h,n,n); the backward is a
+    row-side plus a column-side kernel without atomics.  dedges is only
+    computed when `edges` requires grad."""
+
+    @staticmethod
+    @custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, q, k, v, x, edges, w_e, b_e, mask, scale, eps,
+                grad_enabled):
+        ext = _load_ext()
+        tensors = tuple(_dense16(t) for t in (q, k, v, x, edges, w_e, b_e))
+        mask_c = mask.contiguous() if mask is not None else None
+        # needs_input_grad mirrors requires_grad, also under no_grad, and
+        # grad mode is always off in here: the caller passes the mode it
+        # was called in, so that inference does not write A
+        save = grad_enabled and any(ctx.needs_input_grad)
+        out, dxh, attn = ext.se3_core_fwd(*tensors, scale, eps, mask=mask_c,
+                                          save_attn=save)
+        if save:
+            ctx.save_for_backward(attn, *tensors)
+            ctx.mask = mask_c
+            ctx.scale, ctx.eps = scale, eps
+        return out, dxh
+
+    @staticmethod
+    @custom_bwd(device_type='cuda')
+    @once_differentiable
+    def backward(ctx, dout, ddxh):
+        ext = _load_ext()
+        attn, *tensors = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        grads = ext.se3_core_bwd(_dense16(dout), _dense16(ddxh), attn,
+                                 *tensors, ctx.scale, ctx.eps, mask=ctx.mask,
+                                 need_dedges=need[4])
+        return (*(g if n else None for g, n in zip(grads, need)),
+                None, None, None, None)
+
+
+def hip_se3_core(q, k, v, x, edges, w_e, b_e, scale, eps, mask=None):
+    """q/k/v (b,n,h*dh) as the Linears produce them, x (b,n,3), edges
+    (b,n,n,e), w_e (h,e+1) / b_e (h,) the pair-bias Linear (last column
+    of w_e multiplies |x_i - x_j|^2), mask (b,n) bool over keys or None.
+    Returns (out (b,n,h*dh), dxh (b,n,h,3))."""
+    return _SE3CoreFn.apply(q, k, v, x, edges, w_e, b_e, mask,
+                            float(scale), float(eps),
+                            torch.is_grad_enabled())
+
+
 class _PairRepFn(torch.autograd.Function):
     """Fused pair-rep build (K13): out[b,i,j] = left[i] + right[j] +
     emb[rel[i,j]].  Forward writes the (b,n,n,d) tensor ONCE (the eager

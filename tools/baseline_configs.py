@@ -1,8 +1,11 @@
 """Measure BASELINE.json configs 3-5 on one MI355X (driver runs DP=8).
 
 Runs bench.py as subprocesses with the per-config flags and prints one
-JSON line per config.  Step counts are small — the structure modules
-run eager fp32 (K7 open) and config 5 is crop 512 / msa 512.
+JSON line per config.  Step counts are small: config 5 is crop 512 /
+msa 512 and its EGNN structure module runs the eager fp32 composition.
+Config 4's SE(3) refiner runs the fused attention core (K15,
+ops/hip/se3core.hip; AF2AMD_SE3_FUSED=0 pins its eager composition for
+an A/B).
 """
 import json
 import os
