@@ -123,11 +123,26 @@ class Attention(nn.Module):
             # concatenated per call; the cat is ~1 MB vs 4 GEMM launches)
             w = torch.cat([self.to_q.weight, self.to_kv.weight,
                            self.gating.weight], dim=0)
+
+            inner = self.to_q.weight.shape[0]
+
+            if tie_dim is None:
+                # projection + packed attention + output gate as one
+                # autograd unit: the packed projection has a single
+                # consumer, so its gradient is written once, in place
+                out = ops.attention_core_packed(
+                    None, h, inner, bias=attn_bias, mask=mask,
+                    bias_repeat=attn_bias_repeat, dropout=self.dropout_p,
+                    training=self.training,
+                    gated_input=(x, w, self.gating.bias))
+                if out is not None:
+                    return ops.fused_linear(out, self.to_out.weight,
+                                            self.to_out.bias)
+
             bias_cat = torch.cat([
                 torch.zeros(self.to_q.weight.shape[0] * 3,
                             device=x.device, dtype=self.gating.bias.dtype),
                 self.gating.bias])
-            inner = self.to_q.weight.shape[0]
             fused = F.linear(x, w, bias_cat)
 
             if tie_dim is None:

@@ -82,13 +82,16 @@ def warn_gpu_fallback(opname: str, reason: str):
 
 
 def _attn_unfusable_reason(t, dim_head, bias, drop_p, tie_dim=None,
-                           batch=None):
+                           batch=None, dtype=None):
     """None when the fused attention kernels cover the configuration,
     else the text naming the predicate that failed.  `t` is the bf16
-    q (or packed) tensor; drop_p the ACTIVE dropout rate (0 when off).
-    A missing extension is not judged here (`_want_hip` raises or allows
-    eager for it)."""
+    q (or packed) tensor (`dtype` overrides its dtype when the tensor the
+    kernels will see does not exist yet); drop_p the ACTIVE dropout rate
+    (0 when off).  A missing extension is not judged here (`_want_hip`
+    raises or allows eager for it)."""
     ext = _load_ext()
+    if dtype is None:
+        dtype = t.dtype
     if ext is not None and not hasattr(ext, 'attn_fwd'):
         return 'extension built without attn_fwd'
     if (ext is not None and drop_p > 0.
@@ -100,8 +103,8 @@ def _attn_unfusable_reason(t, dim_head, bias, drop_p, tie_dim=None,
     if not (dim_head <= 64 and dim_head % 8 == 0):
         return (f'dim_head={dim_head} (fused kernel covers '
                 'multiples of 8 up to 64)')
-    if t.dtype != torch.bfloat16:
-        return f'dtype={t.dtype} (fused kernel is bf16)'
+    if dtype != torch.bfloat16:
+        return f'dtype={dtype} (fused kernel is bf16)'
     if bias is not None and bias.dtype != torch.bfloat16:
         return f'bias dtype={bias.dtype} (fused kernel is bf16)'
     if tie_dim is not None and batch % tie_dim != 0:
@@ -140,14 +143,54 @@ def attention_core(q, k, v, bias=None, mask=None, context_mask=None,
                                 dropout=dropout, training=training)
 
 
+# AF2AMD_GATED_ATTN_UNIT=0 keeps gated self-attention on the separate
+# projection / packed attention / gate Functions (A/B measurement)
+_GATED_ATTN_UNIT = os.environ.get("AF2AMD_GATED_ATTN_UNIT", "1") != "0"
+
+
+def _gated_unit_ok(x, w_cat, gate_bias, heads, inner, bias, drop_p):
+    """True when hip_autograd._GatedAttentionUnitFn covers gated
+    self-attention from its input x (B, L, d): switch on, HIP in use,
+    head dim 64, bf16 operands (or fp32 under bf16 autocast) and whatever
+    the fused attention kernels themselves ask for."""
+    return (
+        _GATED_ATTN_UNIT
+        and x.is_cuda and x.dim() == 3
+        and w_cat.shape[0] == 4 * inner
+        and inner == heads * 64
+        and _bf16_ok(x, w_cat, gate_bias)
+        and _attn_unfusable_reason(x, 64, bias, drop_p,
+                                   dtype=torch.bfloat16) is None
+        and using_hip(x, 'attn_gate_bwd')
+    )
+
+
 def attention_core_packed(packed, heads, inner, bias=None, mask=None,
                           context_mask=None, bias_repeat=1, dropout=0.,
-                          training=False):
+                          training=False, gated_input=None):
     """Self-attention consuming a packed [q|k|v|...] projection (B, L, W).
     HIP-only fast path; returns None if not fusable (caller falls back
-    to the split path, whose dispatch names the reason)."""
+    to the split path, whose dispatch names the reason).
+
+    gated_input=(x, w_cat, gate_bias), with packed=None, asks for gated
+    self-attention as ONE autograd unit from the block input x (B, L, d):
+    projection by w_cat = [to_q | to_kv | gating] weights (4 * inner, d),
+    attention core and sigmoid output gate.  Returns the gated
+    (B, L, inner) output, or None when the unit does not cover the
+    configuration (the caller then projects and calls again without
+    gated_input)."""
     key_mask = context_mask if context_mask is not None else mask
     drop_p = float(dropout) if (dropout > 0. and training) else 0.
+    if gated_input is not None:
+        x, w_cat, gate_bias = gated_input
+        if not _gated_unit_ok(x, w_cat, gate_bias, heads, inner, bias,
+                              drop_p):
+            return None
+        from .hip_autograd import hip_attention_packed
+        return hip_attention_packed(None, heads, inner, bias=bias,
+                                    mask=key_mask, bias_repeat=bias_repeat,
+                                    dropout_p=drop_p,
+                                    gated_input=gated_input)
     fusable = (
         packed.is_cuda
         and (inner // heads) == 64

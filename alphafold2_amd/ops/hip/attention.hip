@@ -2009,7 +2009,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  c10::optional<at::Tensor> dv_out,
                                  double dropout_p,
                                  c10::optional<at::Tensor> rng_state,
-                                 c10::optional<int64_t> ds_scratch_bytes) {
+                                 c10::optional<int64_t> ds_scratch_bytes,
+                                 c10::optional<at::Tensor> delta_in) {
   check_qkv_bias(q, k, v, bias, bias_repeat, q_repeat, "attn_bwd");
   const bool has_drop = dropout_p != 0.0;
   BwdDrop<true> dr{};
@@ -2053,7 +2054,18 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   }
   if (dout.stride(3) != 1) dout = dout.contiguous();
 
-  auto delta = at::empty({B, H, Lq}, lse.options());
+  // delta = rowsum(dO * O): computed here, or handed in by a caller whose
+  // own pass over dO and O already formed it (attn_gate_bwd)
+  at::Tensor delta;
+  if (delta_in.has_value()) {
+    delta = *delta_in;
+    TORCH_CHECK(delta.scalar_type() == at::kFloat && delta.is_contiguous() &&
+                delta.numel() == (long)B * H * Lq &&
+                delta.device() == q.device(),
+                "attn_bwd: delta must be contiguous fp32 (B, h, Lq)");
+  } else {
+    delta = at::empty({B, H, Lq}, lse.options());
+  }
   // gradients written through strided views — either caller-provided
   // slices of a packed buffer (no concatenation in autograd) or fresh
   // (B, L, H, DH) memory viewed (B, H, L, DH)
@@ -2139,7 +2151,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
   TViewMut dqv = make_view_mut(dq), dkv = make_view_mut(dk),
            dvv = make_view_mut(dv);
 
-  {
+  if (!delta_in.has_value()) {
     const long rows = (long)B * H * Lq;
     const int block = 256;
     const long grid = (rows * 8 + block - 1) / block;

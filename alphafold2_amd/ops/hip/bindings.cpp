@@ -10,6 +10,8 @@ std::vector<at::Tensor> layernorm_bwd(at::Tensor dy, at::Tensor x,
                                       at::Tensor rstd);
 at::Tensor geglu_fwd(at::Tensor x);
 at::Tensor geglu_bwd(at::Tensor dy, at::Tensor x);
+std::vector<at::Tensor> geglu_bwd_colsum(at::Tensor dy, at::Tensor x);
+long geglu_bwd_colsum_max_h();
 at::Tensor dist_buckets(at::Tensor coords, at::Tensor boundaries);
 at::Tensor pcgemm(at::Tensor A, at::Tensor B, long Bb, long M, long N,
                   long K, long D,
@@ -75,13 +77,22 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  c10::optional<at::Tensor> dv_out,
                                  double dropout_p,
                                  c10::optional<at::Tensor> rng_state,
-                                 c10::optional<int64_t> ds_scratch_bytes);
+                                 c10::optional<int64_t> ds_scratch_bytes,
+                                 c10::optional<at::Tensor> delta);
+std::vector<at::Tensor> attn_gate_bwd(at::Tensor dy, at::Tensor out,
+                                      at::Tensor g, at::Tensor dg_out,
+                                      bool want_colsum);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd, "fused LayerNorm forward (gfx950)");
   m.def("layernorm_bwd", &layernorm_bwd, "fused LayerNorm backward (gfx950)");
   m.def("geglu_fwd", &geglu_fwd, "fused GEGLU forward (gfx950)");
   m.def("geglu_bwd", &geglu_bwd, "fused GEGLU backward (gfx950)");
+  m.def("geglu_bwd_colsum", &geglu_bwd_colsum,
+        "fused GEGLU backward -> [dx, fp32 column sum of the rounded dx] "
+        "(gfx950, bf16)", py::arg("dy"), py::arg("x"));
+  m.def("geglu_bwd_colsum_max_h", &geglu_bwd_colsum_max_h,
+        "largest half width geglu_bwd_colsum covers");
   m.def("dist_buckets", &dist_buckets, "fused cdist+bucketize (gfx950)");
   m.def("pcgemm", &pcgemm,
         "per-channel batched GEMM, stride-parameterized (gfx950 MFMA)");
@@ -172,5 +183,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("rng_state") = c10::nullopt,
         // byte cap of the stored-dS scratch; None = AF2AMD_DS_SCRATCH_BYTES
         // (default 2 GiB), 0 = the float-atomic dBias path
-        py::arg("ds_scratch_bytes") = c10::nullopt);
+        py::arg("ds_scratch_bytes") = c10::nullopt,
+        // rowsum(dO * O) as fp32 (B, h, Lq) when the caller already has it
+        // (attn_gate_bwd): no attn_delta_kernel is launched
+        py::arg("delta") = c10::nullopt);
+  m.def("attn_gate_bwd", &attn_gate_bwd,
+        "gate backward of gated attention in one pass -> [dO, delta"
+        "[, colsum]]; dg goes into dg_out, a slice of the packed gradient "
+        "(gfx950)",
+        py::arg("dy"), py::arg("out"), py::arg("g"), py::arg("dg_out"),
+        py::arg("want_colsum") = false);
 }

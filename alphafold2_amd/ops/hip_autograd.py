@@ -144,7 +144,16 @@ class _FF1GegluFn(torch.autograd.Function):
     def backward(ctx, dy):
         ext = _load_ext()
         x, weight, inter = ctx.saved_tensors
-        di = ext.geglu_bwd(dy.contiguous(), inter)  # (..., N) pre-act grad
+        need_db = ctx.has_bias and ctx.needs_input_grad[2]
+        # the bias gradient is the column sum of di: the kernel that
+        # writes di forms it in the same pass where it covers the width
+        db_sum = None
+        if (need_db and inter.dtype == torch.bfloat16
+                and inter.shape[-1] % 16 == 0
+                and inter.shape[-1] // 2 <= ext.geglu_bwd_colsum_max_h()):
+            di, db_sum = ext.geglu_bwd_colsum(dy.contiguous(), inter)
+        else:
+            di = ext.geglu_bwd(dy.contiguous(), inter)  # pre-act grad
         di2 = di.reshape(-1, di.shape[-1])
         x2 = x.reshape(-1, x.shape[-1])
         dx = dw = db = None
@@ -152,8 +161,9 @@ class _FF1GegluFn(torch.autograd.Function):
             dx = _dgrad(di2, weight).view_as(x)
         if ctx.needs_input_grad[1]:
             dw = _wgrad(di2, x2)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = di2.sum(dim=0)
+        if need_db:
+            db = db_sum.to(di2.dtype) if db_sum is not None \
+                else di2.sum(dim=0)
         return dx, dw, db
 
 
@@ -404,12 +414,113 @@ class _AttentionPackedFn(torch.autograd.Function):
 
 def hip_attention_packed(packed, heads, inner, bias=None, mask=None,
                          bias_repeat=1, dropout_p=0., rng_state=None,
-                         return_rng_state=False):
+                         return_rng_state=False, gated_input=None):
+    """gated_input=(x, w_cat, gate_bias) with packed=None runs projection,
+    attention and output gate as one unit (_GatedAttentionUnitFn) and
+    returns the gated (B, L, inner) output."""
     key_mask = mask.to(torch.uint8) if mask is not None else None
     scale = (inner // heads) ** -0.5
+    if gated_input is not None:
+        x, w_cat, gate_bias = gated_input
+        return _GatedAttentionUnitFn.apply(x, w_cat, gate_bias, bias,
+                                           key_mask, heads, bias_repeat,
+                                           scale, dropout_p, rng_state,
+                                           return_rng_state)
     return _AttentionPackedFn.apply(packed, heads, inner, bias, key_mask,
                                     bias_repeat, scale, dropout_p, rng_state,
                                     return_rng_state)
+
+
+class _GatedAttentionUnitFn(torch.autograd.Function):
+    """Gated self-attention as ONE autograd unit, projection included:
+
+        fused = x @ w_cat.T + [0 | 0 | 0 | gate_bias]     # [q|k|v|gate]
+        y     = attention(q, k, v) * sigmoid(gate)
+
+    The forward issues the calls the separate path issues (the same
+    F.linear, attn_fwd and gatemul_fwd on the same operands).  The value
+    is the BACKWARD: `fused` has a single consumer, so one pass
+    (attn_gate_bwd) writes dgate straight into the gate slice of the
+    packed gradient and hands dO and delta to attn_bwd — no zero fills,
+    no slice copy and no full-width add from autograd, no
+    attn_delta_kernel — and the gating-bias gradient is that pass's
+    column sum instead of a reduce over all four channel blocks."""
+
+    @staticmethod
+    @custom_fwd(device_type='cuda', cast_inputs=torch.bfloat16)
+    def forward(ctx, x, w_cat, gate_bias, bias, mask, heads, bias_repeat,
+                scale, dropout_p=0., rng_state=None, want_state=False):
+        ext = _load_ext()
+        B, L = x.shape[0], x.shape[1]
+        inner = w_cat.shape[0] // 4
+        dh = inner // heads
+        bias_cat = torch.cat([gate_bias.new_zeros(3 * inner), gate_bias])
+        fused = torch.nn.functional.linear(x, w_cat, bias_cat)
+
+        def view(off):
+            return fused.narrow(-1, off, inner) \
+                .view(B, L, heads, dh).permute(0, 2, 1, 3)
+
+        q, k, v = view(0), view(inner), view(2 * inner)
+        bias_c = bias.contiguous() if bias is not None else None
+        mask_c = mask.contiguous() if mask is not None else None
+        out, lse, rng_state = _attn_fwd(ext, ctx, q, k, v, bias_c, mask_c,
+                                        bias_repeat, scale, dropout_p,
+                                        rng_state)
+        # out is (B, h, L, dh) over (B, L, h, dh) memory: a free reshape
+        y = ext.gatemul_fwd(out.permute(0, 2, 1, 3).reshape(B, L, inner),
+                            fused.narrow(-1, 3 * inner, inner),
+                            inner, fused.shape[-1], None)
+        ctx.save_for_backward(x, w_cat, fused, out, lse,
+                              *([bias_c] if bias_c is not None else []))
+        ctx.has_bias = bias_c is not None
+        ctx.mask = mask_c
+        ctx.meta = (heads, inner, bias_repeat, scale)
+        ctx.bias_requires_grad = bias is not None and bias.requires_grad
+        ctx.gate_bias_dtype = gate_bias.dtype
+        return _fn_result(ctx, y, rng_state, want_state)
+
+    @staticmethod
+    @custom_bwd(device_type='cuda')
+    def backward(ctx, dy, *_):
+        ext = _load_ext()
+        saved = ctx.saved_tensors
+        x, w_cat, fused, out, lse = saved[:5]
+        bias = saved[5] if ctx.has_bias else None
+        heads, inner, bias_repeat, scale = ctx.meta
+        B, L, W = fused.shape
+        dh = inner // heads
+        need_dx, need_dw, need_dgb = ctx.needs_input_grad[:3]
+
+        # every channel block is fully overwritten: no fill
+        dpacked = torch.empty_like(fused)
+
+        def view(t, off):
+            return t.narrow(-1, off, inner) \
+                .view(B, L, heads, dh).permute(0, 2, 1, 3)
+
+        rets = ext.attn_gate_bwd(dy.contiguous(), out,
+                                 fused.narrow(-1, 3 * inner, inner),
+                                 dpacked.narrow(-1, 3 * inner, inner),
+                                 need_dgb)
+        d_o, delta = rets[:2]
+        need_dbias = ctx.bias_requires_grad
+        arets = ext.attn_bwd(d_o, view(fused, 0), view(fused, inner),
+                             view(fused, 2 * inner), out, lse, bias, ctx.mask,
+                             bias_repeat, scale, need_dbias,
+                             dq_out=view(dpacked, 0),
+                             dk_out=view(dpacked, inner),
+                             dv_out=view(dpacked, 2 * inner),
+                             delta=delta, **_drop_kw(ctx))
+        dbias = arets[3].to(bias.dtype) if need_dbias else None
+
+        # the two matmuls autograd runs for F.linear
+        dp2 = dpacked.view(-1, W)
+        dx = (dp2 @ w_cat).view_as(x) if need_dx else None
+        dw = dp2.t() @ x.reshape(-1, x.shape[-1]) if need_dw else None
+        dgb = rets[2].to(ctx.gate_bias_dtype) if need_dgb else None
+        return (dx, dw, dgb, dbias, None, None, None, None, None, None,
+                None)
 
 
 def _uniform_row_stride(t):
