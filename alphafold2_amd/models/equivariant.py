@@ -51,7 +51,48 @@ class EGNNLayer(nn.Module):
         nn.init.zeros_(self.coors_mlp[-1].weight)
         nn.init.zeros_(self.coors_mlp[-1].bias)
 
+    def _fused_forward(self, h, x, edges, mask):
+        """Fused fp32 edge-message core (K16), training and inference:
+        one f32-MFMA kernel for the edge part of the first Linear, the
+        distance term, the rest of `edge_mlp`, `coors_mlp` and both sums
+        over j; one for the backward (ops/hip/egnncore.hip).  The first
+        Linear's node columns become two small projections, so neither
+        cat([h_i, h_j, dist2, edges]) nor any (b, n, n, m) activation
+        exists.  The clamp, the coordinate update and `node_mlp` stay in
+        Python autograd.  Returns None when `dispatch.egnn_core_fusable`
+        rejects the configuration (the caller then runs the eager
+        composition)."""
+        from ..ops import dispatch as _dispatch
+        lin1, lin2 = self.edge_mlp[0], self.edge_mlp[2]
+        if not _dispatch.egnn_core_fusable(h, edges,
+                                           m_dim=lin1.out_features):
+            return None
+        from ..ops import hip_autograd
+        b, n, d = h.shape
+        if mask is not None:
+            mask = mask.bool().expand(b, n)
+        # edge_mlp[0].weight columns in cat order: [h_i | h_j | dist2 | edges]
+        w1 = lin1.weight
+        with torch.autocast('cuda', enabled=False):
+            hf = h.float()
+            p = nn.functional.linear(hf, w1[:, :d].float(), lin1.bias.float())
+            q = nn.functional.linear(hf, w1[:, d:2 * d].float())
+        m_i, dx = hip_autograd.hip_egnn_core(
+            p, q, x, edges, w1[:, 2 * d + 1:], w1[:, 2 * d],
+            lin2.weight, lin2.bias, self.coors_mlp[0].weight,
+            self.coors_mlp[0].bias, self.coors_mlp[2].weight,
+            self.coors_mlp[2].bias, self.eps, mask)
+        if self.clamp_coors:
+            dx = dx.clamp(-self.clamp_coors, self.clamp_coors)
+        x = x + dx
+        h = h + self.node_mlp(torch.cat((h, m_i), dim=-1))
+        return h, x
+
     def forward(self, h, x, edges=None, mask=None):
+        fused = self._fused_forward(h, x, edges, mask)
+        if fused is not None:
+            return fused
+
         b, n, d = h.shape
         rel = x[:, :, None, :] - x[:, None, :, :]          # (b, n, n, 3)
         dist2 = rel.pow(2).sum(dim=-1, keepdim=True)       # (b, n, n, 1)

@@ -401,6 +401,54 @@ def se3_core_fusable(h, edges, *, heads, dim_head):
     return False
 
 
+def _egnn_fused_enabled():
+    # read per call so an A/B measurement can flip it inside one process
+    return os.environ.get("AF2AMD_EGNN_FUSED", "1") != "0"
+
+
+def egnn_core_fusable(h, edges, *, m_dim):
+    """Gate of the fused EGNN edge-message core (K16, forward and
+    backward).  Same contract as `se3_core_fusable`: True when
+    `hip_autograd.hip_egnn_core` covers the configuration; otherwise the
+    caller runs the eager composition and, on a GPU with the extension
+    loaded, the failed predicate is named in a fallback warning.
+    AF2AMD_EGNN_FUSED=0 turns the fused path off without a warning (A/B
+    measurement).  Shapes and host-side properties only: no device sync
+    and no look at the capture state.  The kernels tile the keys, so
+    there is no bound on n; the edge dim is bounded by the LDS copy of
+    its weight."""
+    if not _egnn_fused_enabled() or not _want_hip(h):
+        return False
+    ext = _load_ext()
+    edge_dim = edges.shape[-1] if edges is not None else 0
+    autocast = torch.is_autocast_enabled('cuda')
+    if not hasattr(ext, 'egnn_core_bwd'):
+        reason = 'extension built without egnn_core_bwd'
+    elif edges is None:
+        reason = 'edges=None'
+    elif m_dim != 64:
+        reason = f'm_dim={m_dim} (fused kernel covers 64)'
+    elif edge_dim % 64 != 0 or not 64 <= edge_dim <= 512:
+        reason = (f'edge dim {edge_dim} (fused kernel covers multiples '
+                  'of 64 up to 256)')
+    elif edge_dim > ext.egnn_core_max_edge_dim():
+        reason = (f'edge dim {edge_dim} exceeds '
+                  f'{ext.egnn_core_max_edge_dim()}, the widest first-layer '
+                  'weight the kernels stage in LDS (320 to 512 need '
+                  'K-chunked staging)')
+    elif h.dtype == torch.float64:
+        reason = 'dtype=torch.float64 (fused kernel is fp32)'
+    elif not autocast and (h.dtype != torch.float32
+                           or edges.dtype != torch.float32):
+        # under autocast custom_fwd casts every operand to fp32
+        reason = (f'dtype={h.dtype} / edges {edges.dtype} outside autocast '
+                  '(fused kernel is fp32)')
+    else:
+        return True
+    warn_gpu_fallback('egnn_core', reason)
+    return False
+
+
 def layer_norm(x, weight, bias, eps=1e-5):
     if using_hip(x, 'layernorm_fwd'):
         from .hip_autograd import hip_layer_norm

@@ -56,6 +56,17 @@ std::vector<at::Tensor> se3_core_bwd(
     at::Tensor w_e, at::Tensor b_e, double scale, double eps,
     c10::optional<at::Tensor> mask, bool need_dedges);
 long se3_core_max_n(long heads, long dim_head, long edge_dim);
+std::vector<at::Tensor> egnn_core_fwd(
+    at::Tensor P, at::Tensor Q, at::Tensor x, at::Tensor edges,
+    at::Tensor W_e, at::Tensor w_d, at::Tensor W2, at::Tensor b2,
+    at::Tensor Wc1, at::Tensor bc1, at::Tensor Wc2, at::Tensor bc2,
+    double eps, c10::optional<at::Tensor> mask);
+std::vector<at::Tensor> egnn_core_bwd(
+    at::Tensor dm, at::Tensor ddx, at::Tensor P, at::Tensor Q, at::Tensor x,
+    at::Tensor edges, at::Tensor W_e, at::Tensor w_d, at::Tensor W2,
+    at::Tensor b2, at::Tensor Wc1, at::Tensor bc1, at::Tensor Wc2,
+    at::Tensor bc2, double eps, c10::optional<at::Tensor> mask);
+long egnn_core_max_edge_dim();
 at::Tensor pairrep_fwd(at::Tensor left, at::Tensor right, at::Tensor emb,
                        at::Tensor rel);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
@@ -161,6 +172,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "largest sequence length whose SE(3) core forward and backward "
         "fit the device's LDS per block",
         py::arg("heads"), py::arg("dim_head"), py::arg("edge_dim"));
+  m.def("egnn_core_fwd", &egnn_core_fwd,
+        "fused fp32 EGNN edge-message core forward -> [m_i, dx]; writes "
+        "nothing of pair size (gfx950 f32 MFMA, K16)",
+        py::arg("P"), py::arg("Q"), py::arg("x"), py::arg("edges"),
+        py::arg("W_e"), py::arg("w_d"), py::arg("W2"), py::arg("b2"),
+        py::arg("Wc1"), py::arg("bc1"), py::arg("Wc2"), py::arg("bc2"),
+        py::arg("eps"), py::arg("mask") = c10::nullopt);
+  m.def("egnn_core_bwd", &egnn_core_bwd,
+        "fused fp32 EGNN edge-message core backward, recomputing the "
+        "forward -> [dP, dQ, dx, dz1, dw_d, dW2, db2, dWc1, dbc1, dWc2, "
+        "dbc2]; no atomics (gfx950 f32 MFMA, K16)",
+        py::arg("dm"), py::arg("ddx"), py::arg("P"), py::arg("Q"),
+        py::arg("x"), py::arg("edges"), py::arg("W_e"), py::arg("w_d"),
+        py::arg("W2"), py::arg("b2"), py::arg("Wc1"), py::arg("bc1"),
+        py::arg("Wc2"), py::arg("bc2"), py::arg("eps"),
+        py::arg("mask") = c10::nullopt);
+  m.def("egnn_core_max_edge_dim", &egnn_core_max_edge_dim,
+        "largest edge dim whose EGNN core forward and backward fit the "
+        "device's LDS per block");
   m.def("wgrad", &wgrad,
         "split-K weight-gradient GEMM dY^T @ X (gfx950 MFMA, fp32 out)",
         py::arg("dY"), py::arg("X"));

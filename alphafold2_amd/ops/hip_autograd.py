@@ -852,6 +852,65 @@ def hip_se3_core(q, k, v, x, edges, w_e, b_e, scale, eps, mask=None):
                             torch.is_grad_enabled())
 
 
+class _EGNNCoreFn(torch.autograd.Function):
+    """Fused fp32 EGNN edge-message core (K16): first edge Linear on
+    `edges` + distance term + the two 64x64 layers of edge_mlp / coors_mlp
+    + both aggregations in one f32-MFMA kernel.  The forward writes
+    nothing of pair size and saves its inputs only; the backward
+    recomputes the chain in one kernel and stores dz1 (b,n,n,m), from
+    which dedges and dW_e come as library GEMMs.  dedges is only computed
+    when `edges` requires grad."""
+
+    @staticmethod
+    @custom_fwd(device_type='cuda', cast_inputs=torch.float32)
+    def forward(ctx, P, Q, x, edges, W_e, w_d, W2, b2, Wc1, bc1, Wc2, bc2,
+                mask, eps):
+        ext = _load_ext()
+        x = x.contiguous()                  # read as scalars: 4-byte aligned
+        tensors = tuple(_dense16(t) for t in (
+            P, Q, edges, W_e, w_d, W2, b2, Wc1, bc1, Wc2, bc2))
+        P, Q, *rest = tensors
+        tensors = (P, Q, x, *rest)
+        mask_c = mask.contiguous() if mask is not None else None
+        m_i, dx = ext.egnn_core_fwd(*tensors, eps, mask=mask_c)
+        if any(ctx.needs_input_grad):
+            ctx.save_for_backward(*tensors)
+            ctx.mask = mask_c
+            ctx.eps = eps
+        return m_i, dx
+
+    @staticmethod
+    @custom_bwd(device_type='cuda')
+    @once_differentiable
+    def backward(ctx, dm, ddx):
+        ext = _load_ext()
+        tensors = ctx.saved_tensors
+        edges, W_e = tensors[3], tensors[4]
+        need = ctx.needs_input_grad
+        (dP, dQ, dx, dz1, dw_d, dW2, db2, dWc1, dbc1, dWc2,
+         dbc2) = ext.egnn_core_bwd(_dense16(dm), ddx.contiguous(), *tensors,
+                                   ctx.eps, mask=ctx.mask)
+        m = dz1.shape[-1]
+        dz1 = dz1.view(-1, m)
+        dedges = (dz1 @ W_e).view_as(edges) if need[3] else None
+        dW_e = dz1.t() @ edges.view(-1, edges.shape[-1]) if need[4] else None
+        grads = (dP, dQ, dx, dedges, dW_e, dw_d, dW2, db2, dWc1, dbc1, dWc2,
+                 dbc2)
+        return (*(g if n else None for g, n in zip(grads, need)),
+                None, None)
+
+
+def hip_egnn_core(P, Q, x, edges, W_e, w_d, W2, b2, Wc1, bc1, Wc2, bc2, eps,
+                  mask=None):
+    """P = W_i h + b1 and Q = W_j h (b,n,m), x (b,n,3), edges (b,n,n,e);
+    W_e (m,e) / w_d (m,) the edge and distance columns of edge_mlp[0],
+    W2/b2 = edge_mlp[2], Wc1/bc1 = coors_mlp[0], Wc2 (1,m) / bc2 (1,) =
+    coors_mlp[2]; mask (b,n) bool or None.  Returns (m_i (b,n,m), the
+    unclamped dx (b,n,3))."""
+    return _EGNNCoreFn.apply(P, Q, x, edges, W_e, w_d, W2, b2, Wc1, bc1,
+                             Wc2, bc2, mask, float(eps))
+
+
 class _PairRepFn(torch.autograd.Function):
     """Fused pair-rep build (K13): out[b,i,j] = left[i] + right[j] +
     emb[rel[i,j]].  Forward writes the (b,n,n,d) tensor ONCE (the eager

@@ -30,6 +30,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "pairrep.hip"),
         os.path.join(HIP_DIR, "ipacore.hip"),
         os.path.join(HIP_DIR, "se3core.hip"),
+        os.path.join(HIP_DIR, "egnncore.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

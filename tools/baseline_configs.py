@@ -2,10 +2,10 @@
 
 Runs bench.py as subprocesses with the per-config flags and prints one
 JSON line per config.  Step counts are small: config 5 is crop 512 /
-msa 512 and its EGNN structure module runs the eager fp32 composition.
-Config 4's SE(3) refiner runs the fused attention core (K15,
-ops/hip/se3core.hip; AF2AMD_SE3_FUSED=0 pins its eager composition for
-an A/B).
+msa 512.  Its EGNN structure module runs the fused edge-message core
+(K16, ops/hip/egnncore.hip; AF2AMD_EGNN_FUSED=0 pins its eager
+composition for an A/B), and config 4's SE(3) refiner the fused
+attention core (K15, ops/hip/se3core.hip; AF2AMD_SE3_FUSED=0).
 """
 import json
 import os
