@@ -340,20 +340,36 @@ class Alphafold2(nn.Module):
                 b, num_templates, *t_mask_crossed.shape[1:])
 
             # pool over templates with pointwise cross-attention per (i, j)
-            x_point = x.reshape(b * n * n, 1, self.dim)
-            t_point = t.permute(0, 2, 3, 1, 4).reshape(
-                b * n * n, num_templates, self.dim)
             x_mask_point = x_mask.reshape(b * n * n, 1) \
                 if exists(x_mask) else None
             t_mask_point = t_mask_crossed.permute(0, 2, 3, 1).reshape(
                 b * n * n, num_templates)
 
-            template_pooled = self.template_pointwise_attn(
-                x_point,
-                context=t_point,
-                mask=x_mask_point,
-                context_mask=t_mask_point,
-            )
+            # on the GPU the pointwise kernels (K5) take x, t and the
+            # masks in the layouts they have; None = the gate declined
+            template_pooled = None
+            if x.is_cuda:
+                template_pooled = \
+                    self.template_pointwise_attn.pointwise_context(
+                        x.reshape(b, n * n, self.dim),
+                        t.reshape(b, num_templates, n * n, self.dim),
+                        query_mask=x_mask.reshape(b, n * n)
+                        if exists(x_mask) else None,
+                        key_mask=t_mask_crossed.reshape(
+                            b, num_templates, n * n))
+            if exists(template_pooled):
+                template_pooled = template_pooled.reshape(
+                    b * n * n, 1, self.dim)
+            else:
+                x_point = x.reshape(b * n * n, 1, self.dim)
+                t_point = t.permute(0, 2, 3, 1, 4).reshape(
+                    b * n * n, num_templates, self.dim)
+                template_pooled = self.template_pointwise_attn(
+                    x_point,
+                    context=t_point,
+                    mask=x_mask_point,
+                    context_mask=t_mask_point,
+                )
 
             template_pooled_mask = (
                 t_mask_point.sum(dim=-1) > 0)[:, None, None]

@@ -189,6 +189,35 @@ class Attention(nn.Module):
         out = ops.softclamp_gate(out, gates)
         return ops.fused_linear(out, self.to_out.weight, self.to_out.bias)
 
+    def pointwise_context(self, x, context, query_mask=None, key_mask=None):
+        """Cross-attention of ONE query per position over T contexts
+        (template pooling): x (b, P, dim), context (b, T, P, dim),
+        query_mask (b, P), key_mask (b, T, P).  The same function as
+        `forward` on x folded to (b*P, 1, dim) and context to
+        (b*P, T, dim), with the operands left in the layouts they have:
+        nothing is permuted, padded or expanded on the way to
+        ops.template_pointwise_attention.  Returns (b, P, dim), or None
+        on a GPU when `ops.template_pool_fusable` declines (the caller
+        then takes `forward`)."""
+        drop_p = self.dropout_p if (self.dropout_p > 0.
+                                    and self.training) else 0.
+        # gated on the projections' inputs: the gate reads device and
+        # dtype only, which the Linears keep
+        if x.is_cuda:
+            if not ops.template_pool_fusable(
+                    x, context, heads=self.heads, dim_head=self.dim_head,
+                    num_templates=context.shape[1], drop_p=drop_p):
+                return None
+        elif drop_p > 0.:
+            # the op has no attention-prob dropout: forward applies it
+            return None
+        q = self.to_q(x)
+        kv = self.to_kv(context)
+        out = ops.template_pointwise_attention(
+            q, kv, self.heads, key_mask=key_mask, query_mask=query_mask)
+        out = ops.softclamp_gate(out, self.gating(x))
+        return ops.fused_linear(out, self.to_out.weight, self.to_out.bias)
+
 
 class AxialAttention(nn.Module):
     """Row- or column-attention on a (b, h, w, d) grid by folding the

@@ -4,8 +4,10 @@ Every numerically heavy op in the model goes through this package so the
 hand-written CDNA4 HIP kernels can slot in behind a stable interface:
 
 * `attention_core`   — softmax(QK^T * s + bias + mask) @ V (K1/K2 of
-                        SURVEY.md §2.17): MSA row/col, triangle, template
-                        pointwise attention all reduce to this.
+                        SURVEY.md §2.17): MSA row/col and triangle attention
+                        all reduce to this.
+* `template_pointwise_attention` — one query and T keys per pair
+                        position (K5), operands in their projection layouts
 * `geglu`            — chunk + gelu-gate (K6 epilogue)
 * `outer_product_mean` — MSA -> pair communication (K4)
 * `triangle_mix`     — triangle multiplicative einsum (K3)
@@ -26,4 +28,5 @@ from .dispatch import (  # noqa: F401
     pair_outer_sum, pair_rep_build, distance_buckets, layer_norm, softclamp_gate,
     tri_proj_gates,
     fused_linear, ff1_geglu,
+    template_pointwise_attention, template_pool_fusable,
 )

@@ -449,6 +449,107 @@ def egnn_core_fusable(h, edges, *, m_dim):
     return False
 
 
+def _template_pool_fused_enabled():
+    # read per call so an A/B measurement can flip it inside one process
+    return os.environ.get("AF2AMD_TEMPLATE_POOL_FUSED", "1") != "0"
+
+
+# Largest template count the pointwise kernels (K5) are routed to.  It
+# covers constants.MAX_NUM_TEMPLATES (10) with room to spare; it is NOT a
+# measured crossover against the flash tile kernel, whose 64-row K/V tile
+# only starts to fill at several times this count (no T-crossover study
+# has been run; the kernels themselves loop over any T).
+TEMPLATE_POOL_MAX_TEMPLATES = 16
+_TEMPLATE_POOL_HEAD_DIMS = (8, 16, 32, 64)
+
+
+def template_pool_fusable(q, kv, *, heads, dim_head, num_templates, drop_p):
+    """Gate of the template pointwise attention kernels (K5, forward and
+    backward).  True when `hip_autograd.hip_template_pointwise` covers the
+    configuration.  Otherwise the caller takes the folded route through
+    `attention_core`, which is the flash kernels wherever they apply; a
+    fallback warning names the failed predicate only where that route
+    would itself end in the eager composition.
+    AF2AMD_TEMPLATE_POOL_FUSED=0 turns the path off without a warning (A/B
+    measurement).  Same contract as `se3_core_fusable`: shapes and
+    host-side properties only, no device sync and no look at the capture
+    state.  q and kv may be the projections' inputs instead of their
+    outputs: only device and dtype are read from them, and a Linear keeps
+    both."""
+    if not _template_pool_fused_enabled() or not _want_hip(q):
+        return False
+    ext = _load_ext()
+    fp32_pair = q.dtype == torch.float32 and kv.dtype == torch.float32
+    if not hasattr(ext, 'tplattn_bwd'):
+        reason = 'extension built without tplattn_bwd'
+    elif dim_head not in _TEMPLATE_POOL_HEAD_DIMS:
+        # the d / 8 lanes of a (position, head) group must be a power of two
+        reason = (f'dim_head={dim_head} (pointwise kernel covers '
+                  '8, 16, 32 and 64)')
+    elif heads < 1:
+        reason = f'heads={heads}'
+    elif not 1 <= num_templates <= TEMPLATE_POOL_MAX_TEMPLATES:
+        reason = (f'{num_templates} templates (pointwise kernel is routed '
+                  f'up to {TEMPLATE_POOL_MAX_TEMPLATES})')
+    elif not (fp32_pair or _bf16_ok(q, kv)):
+        reason = (f'dtype={q.dtype} / kv {kv.dtype} (pointwise kernel is '
+                  'bf16 or fp32)')
+    elif drop_p > 0.:
+        reason = (f'attention-prob dropout p={drop_p} active (not in the '
+                  'pointwise kernel)')
+    else:
+        return True
+    # today's route is fused too: speak up only where it is not
+    amp = (torch.is_autocast_enabled('cuda')
+           and torch.get_autocast_dtype('cuda') == torch.bfloat16)
+    flash_dtype = torch.bfloat16 if amp and q.is_floating_point() else q.dtype
+    if _attn_unfusable_reason(q, dim_head, None, drop_p,
+                              dtype=flash_dtype) is not None:
+        warn_gpu_fallback('template_pool', reason)
+    return False
+
+
+def template_pointwise_attention(q, kv, heads, key_mask=None,
+                                 query_mask=None):
+    """Attention of ONE query per position over T keys (template pooling).
+
+    * q:  (b, P, H*d), the query projection
+    * kv: (b, T, P, 2*H*d), the [k | v] projection of the T contexts;
+      head h owns channels [h*d, (h+1)*d) of each half
+    * key_mask (b, T, P) / query_mask (b, P): bool, independent, optional
+    Returns (b, P, H*d).  A logit whose key or query is masked is filled
+    with -max before the softmax, so a position with every logit masked
+    averages v over T.  The key mask is applied whether or not a query
+    mask comes with it (eager.attention_core alone applies it only with
+    one, so an all-true query mask is passed along there).
+
+    On gfx950 this is `hip_template_pointwise`; on CPU, or where
+    `template_pool_fusable` declines, the operands are folded to
+    (b*P, H, 1|T, d) for `attention_core`."""
+    b, P, C = q.shape
+    T = kv.shape[1]
+    d = C // heads
+    if q.is_cuda and template_pool_fusable(
+            q, kv, heads=heads, dim_head=d, num_templates=T, drop_p=0.):
+        from .hip_autograd import hip_template_pointwise
+        return hip_template_pointwise(q, kv, heads, key_mask=key_mask,
+                                      query_mask=query_mask)
+    qf = q.reshape(b * P, 1, heads, d).transpose(1, 2)
+    k, v = (t.permute(0, 2, 1, 3).reshape(b * P, T, heads, d).transpose(1, 2)
+            for t in kv.chunk(2, dim=-1))
+    km = qm = None
+    if key_mask is not None:
+        km = key_mask.permute(0, 2, 1).reshape(b * P, T).bool()
+    if query_mask is not None:
+        qm = query_mask.reshape(b * P, 1).bool()
+    if km is not None and qm is None:
+        qm = torch.ones(b * P, 1, dtype=torch.bool, device=q.device)
+    if qm is not None and km is None:
+        km = torch.ones(1, T, dtype=torch.bool, device=q.device)
+    out = attention_core(qf, k, v, mask=qm, context_mask=km)
+    return out.transpose(1, 2).reshape(b, P, C)
+
+
 def layer_norm(x, weight, bias, eps=1e-5):
     if using_hip(x, 'layernorm_fwd'):
         from .hip_autograd import hip_layer_norm

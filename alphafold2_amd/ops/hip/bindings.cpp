@@ -93,6 +93,14 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
 std::vector<at::Tensor> attn_gate_bwd(at::Tensor dy, at::Tensor out,
                                       at::Tensor g, at::Tensor dg_out,
                                       bool want_colsum);
+std::vector<at::Tensor> tplattn_fwd(at::Tensor q, at::Tensor kv, long heads,
+                                    c10::optional<at::Tensor> key_mask,
+                                    c10::optional<at::Tensor> query_mask);
+std::vector<at::Tensor> tplattn_bwd(at::Tensor dout, at::Tensor q,
+                                    at::Tensor kv, at::Tensor out,
+                                    at::Tensor lse, long heads,
+                                    c10::optional<at::Tensor> key_mask,
+                                    c10::optional<at::Tensor> query_mask);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layernorm_fwd", &layernorm_fwd, "fused LayerNorm forward (gfx950)");
@@ -223,4 +231,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "(gfx950)",
         py::arg("dy"), py::arg("out"), py::arg("g"), py::arg("dg_out"),
         py::arg("want_colsum") = false);
+  m.def("tplattn_fwd", &tplattn_fwd,
+        "template pointwise attention forward, one query and T keys per "
+        "pair position, operands in their projection layouts -> [out, lse] "
+        "(gfx950, bf16 / fp32, K5)",
+        py::arg("q"), py::arg("kv"), py::arg("heads"),
+        py::arg("key_mask") = c10::nullopt,
+        py::arg("query_mask") = c10::nullopt);
+  m.def("tplattn_bwd", &tplattn_bwd,
+        "template pointwise attention backward -> [dq, dkv]; dkv is one "
+        "tensor in kv's layout, no atomics (gfx950, bf16 / fp32, K5)",
+        py::arg("dout"), py::arg("q"), py::arg("kv"), py::arg("out"),
+        py::arg("lse"), py::arg("heads"),
+        py::arg("key_mask") = c10::nullopt,
+        py::arg("query_mask") = c10::nullopt);
 }

@@ -941,3 +941,57 @@ class _PairRepFn(torch.autograd.Function):
 
 def hip_pair_rep(left, right, emb, rel):
     return _PairRepFn.apply(left, right, emb, rel)
+
+
+def _byte_mask(mask):
+    """bool / uint8 mask as the contiguous one-byte tensor the kernels
+    read; a contiguous bool mask is passed as it is (no copy)."""
+    if mask is None:
+        return None
+    if mask.dtype not in (torch.bool, torch.uint8):
+        mask = mask != 0
+    return mask.contiguous()
+
+
+class _TemplatePointwiseFn(torch.autograd.Function):
+    """Template pointwise attention (K5): one query and T keys per pair
+    position, q (b, P, H*d) and kv (b, T, P, 2*H*d) consumed in the
+    layouts the projections produce (through their strides: nothing is
+    permuted, padded or copied).  bf16 or fp32 storage, fp32 math.
+    Forward keeps q, kv, out and lse (b, P, H); backward is one kernel
+    writing dq and ONE dkv in kv's layout, so there is no split-backward
+    concatenation.  The masks are not differentiable inputs and stay on
+    ctx as the caller's own tensors."""
+
+    @staticmethod
+    @custom_fwd(device_type='cuda', cast_inputs=torch.bfloat16)
+    def forward(ctx, q, kv, key_mask, query_mask, heads):
+        ext = _load_ext()
+        key_mask, query_mask = _byte_mask(key_mask), _byte_mask(query_mask)
+        out, lse = ext.tplattn_fwd(q, kv, heads, key_mask=key_mask,
+                                   query_mask=query_mask)
+        ctx.save_for_backward(q, kv, out, lse)
+        ctx.key_mask, ctx.query_mask = key_mask, query_mask
+        ctx.heads = heads
+        return out
+
+    @staticmethod
+    @custom_bwd(device_type='cuda')
+    @once_differentiable
+    def backward(ctx, dout):
+        ext = _load_ext()
+        q, kv, out, lse = ctx.saved_tensors
+        dout = _dense16(dout.to(q.dtype))
+        dq, dkv = ext.tplattn_bwd(dout, q, kv, out, lse, ctx.heads,
+                                  key_mask=ctx.key_mask,
+                                  query_mask=ctx.query_mask)
+        return dq, dkv, None, None, None
+
+
+def hip_template_pointwise(q, kv, heads, key_mask=None, query_mask=None):
+    """q (b, P, H*d), kv (b, T, P, 2*H*d) = [k | v], key_mask (b, T, P)
+    and query_mask (b, P) bool / uint8 or None.  Returns out (b, P, H*d).
+    Operands need a dense last dim and 16-byte aligned rows; the launcher
+    raises otherwise."""
+    return _TemplatePointwiseFn.apply(q, kv, key_mask, query_mask,
+                                      int(heads))

@@ -31,6 +31,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "ipacore.hip"),
         os.path.join(HIP_DIR, "se3core.hip"),
         os.path.join(HIP_DIR, "egnncore.hip"),
+        os.path.join(HIP_DIR, "tplattn.hip"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
