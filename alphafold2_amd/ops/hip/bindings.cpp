@@ -16,7 +16,8 @@ at::Tensor dist_buckets(at::Tensor coords, at::Tensor boundaries);
 at::Tensor pcgemm(at::Tensor A, at::Tensor B, long Bb, long M, long N,
                   long K, long D,
                   long a_bs, long a_ms, long a_ks,
-                  long b_bs, long b_ns, long b_ks, double alpha);
+                  long b_bs, long b_ns, long b_ks, double alpha,
+                  long variant);
 at::Tensor gatemul_fwd(at::Tensor x, at::Tensor g, long xs, long gs,
                        c10::optional<at::Tensor> rowmask);
 std::vector<at::Tensor> gatemul_bwd(at::Tensor dy, at::Tensor x, at::Tensor g,
@@ -114,7 +115,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "largest half width geglu_bwd_colsum covers");
   m.def("dist_buckets", &dist_buckets, "fused cdist+bucketize (gfx950)");
   m.def("pcgemm", &pcgemm,
-        "per-channel batched GEMM, stride-parameterized (gfx950 MFMA)");
+        "per-channel batched GEMM, stride-parameterized (gfx950 MFMA); "
+        "variant 1 = scatter staging, 2 = wide stores, 3 = full lines, "
+        "0 = default",
+        py::arg("A"), py::arg("B"), py::arg("Bb"), py::arg("M"), py::arg("N"),
+        py::arg("K"), py::arg("D"), py::arg("a_bs"), py::arg("a_ms"),
+        py::arg("a_ks"), py::arg("b_bs"), py::arg("b_ns"), py::arg("b_ks"),
+        py::arg("alpha"), py::arg("variant") = 0);
   m.def("gatemul_fwd", &gatemul_fwd, "fused x*sigmoid(g) forward (gfx950)",
         py::arg("x"), py::arg("g"), py::arg("xs"), py::arg("gs"),
         py::arg("rowmask") = c10::nullopt);

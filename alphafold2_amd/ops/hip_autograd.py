@@ -573,16 +573,19 @@ def hip_gatemul(x, g, rowmask=None):
     return _GateMulFn.apply(x, g, rowmask)
 
 
-def _pcg(A, B, M, N, K, a_m, a_k, b_n, b_k, alpha=1.0):
+def _pcg(A, B, M, N, K, a_m, a_k, b_n, b_k, alpha=1.0, variant=0):
     """Invoke the per-channel GEMM: C[b,m,n,d] = alpha * sum_k A*B where
     a_m/a_k (b_n/b_k) are the AXIS INDICES (1 or 2) of A (B) that play
-    the output-m (output-n) and contraction roles."""
+    the output-m (output-n) and contraction roles.  variant picks the
+    kernel for A/B runs and tests: 1 = scatter staging, 2 = wide stores,
+    3 = full lines, 0 = the extension's default."""
     ext = _load_ext()
     D = A.shape[-1]
     Bb = A.shape[0]
     return ext.pcgemm(A, B, Bb, M, N, K, D,
                       A.stride(0), A.stride(a_m), A.stride(a_k),
-                      B.stride(0), B.stride(b_n), B.stride(b_k), alpha)
+                      B.stride(0), B.stride(b_n), B.stride(b_k), alpha,
+                      variant)
 
 
 def _pc_ok(*ts):
