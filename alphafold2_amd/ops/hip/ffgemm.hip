@@ -295,6 +295,9 @@ at::Tensor linear_fwd(at::Tensor x, at::Tensor W,
   TORCH_CHECK(W.size(1) == K, "linear_fwd: K mismatch");
   TORCH_CHECK(K % 8 == 0 && N % 8 == 0,
               "linear_fwd: K and N must be multiples of 8");
+  TORCH_CHECK(stage != 1 || K % 64 == 0,
+              "linear_fwd: stage 1 (DMA staging) reads whole 64-wide K "
+              "slabs, K = ", K, " is no multiple of 64");
 
   auto sizes = x.sizes().vec();
   sizes.back() = N;
@@ -347,6 +350,9 @@ std::vector<at::Tensor> ff1_geglu_fwd(at::Tensor x, at::Tensor W,
   const int N = W.size(0);
   TORCH_CHECK(W.size(1) == K && N % 16 == 0, "ff1_geglu_fwd: bad W shape");
   TORCH_CHECK(K % 8 == 0, "ff1_geglu_fwd: K must be a multiple of 8");
+  TORCH_CHECK(stage != 1 || K % 64 == 0,
+              "ff1_geglu_fwd: stage 1 (DMA staging) reads whole 64-wide K "
+              "slabs, K = ", K, " is no multiple of 64");
 
   auto osz = x.sizes().vec();
   osz.back() = N / 2;

@@ -41,13 +41,19 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
     const T* xr = x + row * D;
     T* yr = y + row * D;
 
+    // Single pass over deviations from the row's first element: with
+    // raw sums, sumsq / D - mean^2 cancels to noise (or below zero) once
+    // |mean| >> spread.  Shifted, both sums are of the order of the
+    // spread and the subtraction below loses nothing that matters (the
+    // shift is an element of the row, so (mean - shift)^2 <= D * var).
+    const float shift = to_f32(xr[0]);
     float sum = 0.f, sumsq = 0.f;
     for (int i = lane * VEC; i < D; i += GROUP * VEC) {
       T xv[VEC];
       vload<T, VEC>(xr + i, xv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        float v = to_f32(xv[k]);
+        float v = to_f32(xv[k]) - shift;
         sum += v;
         sumsq += v * v;
       }
@@ -55,11 +61,11 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
     sum = group_sum<GROUP>(sum);
     sumsq = group_sum<GROUP>(sumsq);
 
-    const float mean = sum / D;
-    const float var = sumsq / D - mean * mean;
+    const float dmean = sum / D;           // mean - shift
+    const float var = fmaxf(sumsq / D - dmean * dmean, 0.f);
     const float rstd = rsqrtf(var + eps);
     if (lane == 0) {
-      mean_out[row] = mean;
+      mean_out[row] = shift + dmean;
       rstd_out[row] = rstd;
     }
 
@@ -68,7 +74,7 @@ __global__ void layernorm_fwd_kernel(const T* __restrict__ x,
       vload<T, VEC>(xr + i, xv);
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
-        float xhat = (to_f32(xv[k]) - mean) * rstd;
+        float xhat = ((to_f32(xv[k]) - shift) - dmean) * rstd;
         yv[k] = from_f32<T>(xhat * w[i + k] + b[i + k]);
       }
       vstore<T, VEC>(yr + i, yv);
@@ -100,6 +106,22 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
 #pragma unroll
     for (int k = 0; k < VEC; ++k) dw_loc[c][k] = db_loc[c][k] = 0.f;
 
+  // dw/db: write one PARTIAL row per block (no global same-address
+  // atomics — 2048 serialized RMW chains per column measured 3.2 ms on
+  // HW vs 21 us without; tools/ln_bench.hip).  A small tree-reduce
+  // kernel folds the (grid, D) partials afterwards.
+  float* dwp = dw + (long)blockIdx.x * D;  // dw points at partials here
+  float* dbp = db + (long)blockIdx.x * D;
+  const bool lds_combine = (256 * VEC <= 4096) && (D <= GROUP * VEC);
+  if (!lds_combine) {
+    // the partial row takes atomics (from the huge-D tail inside the row
+    // loop and from the register chunks after it): zero it first
+    if (threadIdx.x < GROUP) {
+      for (int i = threadIdx.x; i < D; i += GROUP) dwp[i] = dbp[i] = 0.f;
+    }
+    __syncthreads();
+  }
+
   for (long row = (long)blockIdx.x * RPB + grp; row < rows;
        row += (long)gridDim.x * RPB) {
     const T* dyr = dy + row * D;
@@ -127,7 +149,8 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
         }
       }
     }
-    // huge-D tail beyond the register-held chunks: direct atomics
+    // huge-D tail beyond the register-held chunks: atomics straight into
+    // the block's own (pre-zeroed) partial row
     for (int i = (MAXCHUNK * GROUP + lane) * VEC; i < D; i += GROUP * VEC) {
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
@@ -136,8 +159,8 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
         float gw = g * w[i + k];
         c1 += gw;
         c2 += gw * xhat;
-        atomicAdd(&dw[i + k], g * xhat);
-        atomicAdd(&db[i + k], g);
+        atomicAdd(&dwp[i + k], g * xhat);
+        atomicAdd(&dbp[i + k], g);
       }
     }
     c1 = group_sum<GROUP>(c1) / D;
@@ -157,14 +180,7 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
     }
   }
 
-  // dw/db: write one PARTIAL row per block (no global same-address
-  // atomics — 2048 serialized RMW chains per column measured 3.2 ms on
-  // HW vs 21 us without; tools/ln_bench.hip).  A small tree-reduce
-  // kernel folds the (grid, D) partials afterwards.
   __shared__ float red[256 * VEC > 4096 ? 1 : 256 * VEC];  // dw then db
-  float* dwp = dw + (long)blockIdx.x * D;  // dw points at partials here
-  float* dbp = db + (long)blockIdx.x * D;
-  const bool lds_combine = (256 * VEC <= 4096) && (D <= GROUP * VEC);
   if (lds_combine) {
     // each thread owns exactly VEC columns (chunk 0); combine the RPB
     // groups through LDS, then one coalesced partial-row store
@@ -196,12 +212,8 @@ __global__ void layernorm_bwd_kernel(const T* __restrict__ dy,
         for (int k = 0; k < VEC; ++k) dbp[i + k] = db_loc[0][k];
     }
   } else {
-    // rare large-D path: per-block atomics into the partial row
-    // (contention = RPB groups only)
-    if (threadIdx.x < GROUP) {
-      for (int i = threadIdx.x; i < D; i += GROUP) dwp[i] = dbp[i] = 0.f;
-    }
-    __syncthreads();
+    // rare large-D path: per-block atomics into the partial row zeroed
+    // above (contention = RPB groups only)
 #pragma unroll
     for (int chunk = 0; chunk < MAXCHUNK; ++chunk) {
       const int i = (chunk * GROUP + lane) * VEC;
