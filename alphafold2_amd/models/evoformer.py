@@ -264,7 +264,9 @@ class AxialAttention(nn.Module):
         # reference alphafold2.py:248)
         attn_bias = None
         if exists(self.edges_to_attn_bias) and exists(edges):
-            bias = self.edges_to_attn_bias[0](edges)         # (b, i, j, heads)
+            # (b, i, j, heads); through ops.fused_linear for its backward
+            # (the weight gradient reduces over all b * i * j pair rows)
+            bias = ops.fused_linear(edges, self.edges_to_attn_bias[0].weight)
             attn_bias = bias.permute(0, 3, 1, 2).contiguous()
 
         tie_dim = axial_dim if self.global_query_attn else None
@@ -324,7 +326,7 @@ class TriangleMultiplicativeModule(nn.Module):
                               self.left_gate.bias, self.right_gate.bias,
                               self.out_gate.bias])
         hdim = self.left_proj.weight.shape[0]
-        fused = F.linear(x, w, bias_cat)
+        fused = ops.fused_linear(x, w, bias_cat)
         # packed gated projections: the pair mask folds into the gate
         # kernel, and the backward writes both gatemul gradients into
         # one packed buffer (no SplitBackward concatenation)
@@ -356,7 +358,8 @@ class OuterMean(nn.Module):
         w = torch.cat([self.left_proj.weight, self.right_proj.weight], dim=0)
         bias_cat = torch.cat([self.left_proj.bias, self.right_proj.bias])
         hdim = self.left_proj.weight.shape[0]
-        left, right = F.linear(x, w, bias_cat).split([hdim, hdim], dim=-1)
+        left, right = ops.fused_linear(x, w, bias_cat).split(
+            [hdim, hdim], dim=-1)
         outer = ops.outer_product_mean(left, right, mask=mask, eps=self.eps)
         return ops.fused_linear(outer, self.proj_out.weight,
                                 self.proj_out.bias)

@@ -235,8 +235,8 @@ def fused_linear(x, weight, bias=None, residual=None):
     128x128 GEMM on plain/residual FORWARDS, so _LinearFn runs Tensile
     forward by default (AF2AMD_CUSTOM_LINEAR=1 forces the custom GEMM
     for A/B work); the routing still pays in backward, where the
-    split-K wgrad kernel takes the small-output/huge-K gradient class
-    Tensile runs at ~98 TF."""
+    streaming split-K wgrad kernel takes the huge-K weight gradient and
+    returns the bias gradient from the same pass."""
     ok = (x.shape[-1] % 8 == 0 and weight.shape[0] % 8 == 0
           and _bf16_ok(x, weight, residual)
           and using_hip(x, 'linear_fwd'))

@@ -33,6 +33,8 @@ std::vector<at::Tensor> ff1_geglu_fwd(at::Tensor x, at::Tensor W,
                                       c10::optional<at::Tensor> bias,
                                       long stage, bool want_inter);
 at::Tensor wgrad(at::Tensor dY, at::Tensor X);
+at::Tensor wgrad_v1(at::Tensor dY, at::Tensor X);
+std::vector<at::Tensor> wgrad_colsum(at::Tensor dY, at::Tensor X);
 std::vector<at::Tensor> ipa_core_fwd(
     at::Tensor q_s, at::Tensor k_s, at::Tensor v_s, at::Tensor q_pg,
     at::Tensor k_pg, at::Tensor v_pg, at::Tensor bias, at::Tensor pair,
@@ -207,7 +209,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "largest edge dim whose EGNN core forward and backward fit the "
         "device's LDS per block");
   m.def("wgrad", &wgrad,
-        "split-K weight-gradient GEMM dY^T @ X (gfx950 MFMA, fp32 out)",
+        "split-K weight-gradient GEMM dY^T @ X (gfx950 MFMA, fp32 out): "
+        "the streaming kernel with a fixed-order fold, or the r02 kernel "
+        "under AF2AMD_WGRAD_V1=1",
+        py::arg("dY"), py::arg("X"));
+  m.def("wgrad_v1", &wgrad_v1,
+        "the r02 split-K weight-gradient kernel (fp32 atomic drain)",
+        py::arg("dY"), py::arg("X"));
+  m.def("wgrad_colsum", &wgrad_colsum,
+        "streaming split-K weight gradient -> [dW (M, N), sum_k dY[k, :] "
+        "(M,)] fp32 from one pass over dY and X",
         py::arg("dY"), py::arg("X"));
   m.def("attn_fwd", &attn_fwd, "fused flash attention forward (gfx950)",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("bias"),

@@ -53,21 +53,49 @@ def _dgrad(dy2, weight):
     return dy2 @ weight
 
 
-def _wgrad(dy2, x2):
-    """dW = dY^T @ X.  The custom split-K kernel wins ONLY the
-    small-output / huge-K class (measured: (256, 512) 0.64 vs 0.88 ms;
-    (2048, 256) and (256, 1024) lose — profiles/r02_ffgemm_ab.log),
-    so dispatch is gated to that class."""
+import os as _os
+
+# AF2AMD_WGRAD_V1=1: the r02 atomic-drain kernel behind its r02 gate, and
+# bias gradients as separate reductions (A/B switch for the r09 kernel)
+_WGRAD_V1 = _os.environ.get("AF2AMD_WGRAD_V1", "0") == "1"
+
+# largest dW (elements) the streaming kernel takes: the largest measured
+_WGRAD_STREAM_MAX_MN = 2048 * 256
+_WGRAD_V1_MAX_MN = 256 * 512
+
+
+def _wgrad(dy2, x2, want_colsum=False):
+    """dW = dY^T @ X, and with want_colsum (dW, colsum) where colsum is
+    the fp32 column sum of dY out of the same pass when the kernel ran,
+    else None.
+
+    K >= 65536 with dW up to 2048 x 256 elements goes to the streaming
+    split-K kernel (wgrad.hip): one pass over dY and X, partials folded
+    in a fixed order, so dW is the same on every run.  That is every
+    Linear weight gradient of the trunk; at batch 5 the kernel runs them
+    in 0.03-0.48 ms against 0.28-0.89 ms of the library GEMM and
+    0.16-2.46 ms of the r02 kernel (tools/wgrad_bench.py,
+    profiles/r09_wgrad_ab.log).  Larger outputs are not measured and
+    small K stays on the library GEMM.  AF2AMD_WGRAD_V1=1 restores the
+    r02 kernel and its gate (M * N <= 256 * 512)."""
     M, N = dy2.shape[-1], x2.shape[-1]
     K = dy2.shape[0]
-    if (M * N <= 256 * 512 and K >= 65536 and M % 8 == 0 and N % 8 == 0
+    dw = cs = None
+    if (K >= 65536 and M % 8 == 0 and N % 8 == 0
             and dy2.dtype == torch.bfloat16):
-        ext = _load_ext()
-        return ext.wgrad(dy2.contiguous(), x2.contiguous())
-    return dy2.t() @ x2
+        if _WGRAD_V1:
+            if M * N <= _WGRAD_V1_MAX_MN:
+                dw = _load_ext().wgrad_v1(dy2.contiguous(), x2.contiguous())
+        elif M * N <= _WGRAD_STREAM_MAX_MN:
+            ext = _load_ext()
+            if want_colsum:
+                dw, cs = ext.wgrad_colsum(dy2.contiguous(), x2.contiguous())
+            else:
+                dw = ext.wgrad(dy2.contiguous(), x2.contiguous())
+    if dw is None:
+        dw = dy2.t() @ x2
+    return (dw, cs) if want_colsum else dw
 
-
-import os as _os
 
 _FORCE_CUSTOM_LINEAR_FWD = _os.environ.get(
     "AF2AMD_CUSTOM_LINEAR", "0") == "1"
@@ -80,7 +108,8 @@ class _LinearFn(torch.autograd.Function):
     plain/residual shapes) unless AF2AMD_CUSTOM_LINEAR=1; the value of
     routing plain Linears through this Function is the BACKWARD: the
     split-K wgrad kernel takes the small-output/huge-K gradients that
-    Tensile handles poorly (~98 TF on the attention out-projection)."""
+    Tensile handles poorly, and hands back the bias gradient (the column
+    sum of dY) from the same pass."""
 
     @staticmethod
     @custom_fwd(device_type='cuda', cast_inputs=torch.bfloat16)
@@ -107,12 +136,19 @@ class _LinearFn(torch.autograd.Function):
         dy2 = dy.contiguous().reshape(-1, dy.shape[-1])
         x2 = x.reshape(-1, x.shape[-1])
         dx = dw = db = None
+        need_db = ctx.has_bias and ctx.needs_input_grad[2]
+        # dW before dX: the kernel's split-K partials are free again when
+        # the (larger) dX is allocated
+        if ctx.needs_input_grad[1] and need_db:
+            dw, colsum = _wgrad(dy2, x2, want_colsum=True)
+            if colsum is not None:
+                db = colsum.to(dy2.dtype)
+        elif ctx.needs_input_grad[1]:
+            dw = _wgrad(dy2, x2)
+        if need_db and db is None:
+            db = dy2.sum(dim=0)
         if ctx.needs_input_grad[0]:
             dx = _dgrad(dy2, weight).view_as(x)
-        if ctx.needs_input_grad[1]:
-            dw = _wgrad(dy2, x2)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dy2.sum(dim=0)
         dr = dy if ctx.has_resid else None
         return dx, dw, db, dr
 
@@ -157,10 +193,10 @@ class _FF1GegluFn(torch.autograd.Function):
         di2 = di.reshape(-1, di.shape[-1])
         x2 = x.reshape(-1, x.shape[-1])
         dx = dw = db = None
+        if ctx.needs_input_grad[1]:
+            dw = _wgrad(di2, x2)   # before dX, as in _LinearFn
         if ctx.needs_input_grad[0]:
             dx = _dgrad(di2, weight).view_as(x)
-        if ctx.needs_input_grad[1]:
-            dw = _wgrad(di2, x2)
         if need_db:
             db = db_sum.to(di2.dtype) if db_sum is not None \
                 else di2.sum(dim=0)
@@ -516,8 +552,8 @@ class _GatedAttentionUnitFn(torch.autograd.Function):
 
         # the two matmuls autograd runs for F.linear
         dp2 = dpacked.view(-1, W)
+        dw = _wgrad(dp2, x.reshape(-1, x.shape[-1])) if need_dw else None
         dx = (dp2 @ w_cat).view_as(x) if need_dx else None
-        dw = dp2.t() @ x.reshape(-1, x.shape[-1]) if need_dw else None
         dgb = rets[2].to(ctx.gate_bias_dtype) if need_dgb else None
         return (dx, dw, dgb, dbias, None, None, None, None, None, None,
                 None)
