@@ -72,8 +72,9 @@ class FeedForward(nn.Module):
         init_zero_(self.net[-1])
 
     def forward(self, x, residual=None, **kwargs):
-        """`residual`, when given, is added inside the output GEMM's
-        epilogue (saves a full elementwise pass over the tensor)."""
+        """`residual`, when given, is added to the output GEMM's result by
+        ops.fused_linear: a separate elementwise `out + residual` after
+        the GEMM (`_LinearFn.forward`), not a GEMM epilogue."""
         x = self.norm(x)
         h = ops.ff1_geglu(x, self.net[0].weight, self.net[0].bias)
         h = self.net[2](h)
@@ -443,7 +444,8 @@ class EvoformerBlock(nn.Module):
             and torch.is_grad_enabled()
 
         def run_ff(f, t):
-            # residual folded into the FF output GEMM's epilogue
+            # residual added by ops.fused_linear after the FF output GEMM
+            # (a separate elementwise pass, not the GEMM's epilogue)
             if ckpt_ff:
                 return checkpoint(lambda u: f(u, residual=u), t,
                                   use_reentrant=False,

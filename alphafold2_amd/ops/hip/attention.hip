@@ -40,6 +40,7 @@
 #include <ATen/hip/HIPGraphsUtils.cuh>
 
 #include "attn_dropout.h"
+#include "colsum.h"
 #include "common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1414,6 +1415,202 @@ void attn_dbias_sum_kernel(DsView ds, float* __restrict__ dbias,
 }
 
 // ---------------------------------------------------------------------------
+// dQ from stored dS with the dBias sum taken on the way (r10): the dQ
+// kernel already holds every dS element in registers on its way to LDS,
+// so the sum needs no second read of the scratch.  A block owns a q
+// tile, a (repeat group, head) and a chunk of `epb` consecutive batch
+// entries of that group inside the slice [b0, b1).  Per entry it forms
+// and writes dQ exactly as attn_bwd_dq_from_ds_kernel does (same MFMA
+// order, same scale on the accumulator: bit-equal, whatever the chunking
+// and slicing); the staging pipeline runs on across entries.  Across its
+// entries it keeps the fp32 sum of the dS it staged, 16 values per
+// thread and kv tile, so NKV = ceil(Lk / 64) is a template parameter and
+// at most DQ_DBIAS_MAX_NKV.  The sums, dQ's accumulators and the two
+// staged tiles come to 210 VGPRs at the flagship's four tiles (2
+// waves/SIMD; holding the kernel to 3 waves/SIMD spills 152 bytes per
+// lane); five and six tiles spill 56 and 64 bytes at the 256 of 2
+// waves/SIMD, which is why automatic stops at four.  After the last
+// entry every kv tile is transposed through LDS as in
+// attn_dbias_sum_kernel.  With `direct` (one chunk per group) the block
+// is the only writer of its dbias elements and adds to a group that an
+// earlier slice started; otherwise it stores its partial
+// [chunk][group in slice][head][Lq][Lk] and colsum_fold_launch adds the
+// chunks in order.  A chunk past the group's last entry of the slice
+// stores zeros.
+
+__device__ __forceinline__ void ds_sum_add(const float4& v, float* a) {
+  const unsigned int u[4] = {__float_as_uint(v.x), __float_as_uint(v.y),
+                             __float_as_uint(v.z), __float_as_uint(v.w)};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    a[2 * i] += __uint_as_float(u[i] << 16);
+    a[2 * i + 1] += __uint_as_float(u[i] & 0xffff0000u);
+  }
+}
+
+constexpr int DQ_DBIAS_MAX_NKV = 6;
+
+// stage_load / stage_load_rc from a wave-uniform tile base and the
+// thread's two 32-bit element offsets, which are the same for every tile
+// and entry: the tile bases stay in scalar registers
+__device__ __forceinline__ void stage_load_off(const bf16_t* __restrict__ g,
+                                               const unsigned (&off)[2],
+                                               int rows, bool col_ok0,
+                                               bool col_ok1, StageRegs& r) {
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int row = (threadIdx.x + pass * 256) >> 3;
+    float4 val = {0, 0, 0, 0};
+    if (row < rows && (pass ? col_ok1 : col_ok0))
+      val = *reinterpret_cast<const float4*>(g + off[pass]);
+    (pass ? r.v1 : r.v0) = val;
+  }
+}
+
+template <int NKV>
+__global__ __launch_bounds__(256, 2)
+void attn_bwd_dq_dbias_kernel(DsView ds, TView k, TViewMut dq,
+                              float* __restrict__ sum_out, long chunk_stride,
+                              int Lq, int Lk, int heads, float scale,
+                              int bias_repeat, int b0, int b1, int g0,
+                              int epb, int direct, int accumulate) {
+  // [0], [1]: dS tiles [kv][q]; [2], [3]: K tiles [kv][d]; the fp32
+  // transposition tile of the epilogue lies over them
+  __shared__ __attribute__((aligned(16))) char lds[4][BK * ROWB];
+  static_assert(sizeof(float) * BQ * (BK + 1) <= 4 * BK * ROWB, "tile");
+
+  const int qtile = blockIdx.x;
+  const int gl = blockIdx.y / heads;
+  const int head = blockIdx.y - gl * heads;
+  const int g = g0 + gl;
+  const int r_lo = max(g * bias_repeat, b0);
+  const int r_hi = min((g + 1) * bias_repeat, b1);
+  const int e_lo = r_lo + blockIdx.z * epb;
+  const int e_hi = min(e_lo + epb, r_hi);
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int q_rows = min(BQ, Lq - qtile * BQ);
+
+  float sum[NKV][16];
+#pragma unroll
+  for (int t = 0; t < NKV; ++t)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) sum[t][j] = 0.f;
+
+  unsigned ds_off[2], k_off[2];
+  bool col_ok[2];
+#pragma unroll
+  for (int pass = 0; pass < 2; ++pass) {
+    const int idx = threadIdx.x + pass * 256;
+    const int row = idx >> 3;
+    const int c8 = (idx & 7) << 3;
+    ds_off[pass] = (unsigned)row * (unsigned)ds.pitch + c8;
+    k_off[pass] = (unsigned)row * (unsigned)k.rs + c8;
+    col_ok[pass] = c8 < q_rows;
+  }
+
+  StageRegs dsreg, kreg;
+  if (e_lo < e_hi) {
+    stage_load_off(ds.p + ((long)(e_lo - b0) * heads + head) * ds.plane
+                       + qtile * BQ,
+                   ds_off, min(BK, Lk), col_ok[0], col_ok[1], dsreg);
+    stage_load_off(k.base(e_lo, head), k_off, min(BK, Lk), true, true, kreg);
+  }
+  int buf = 0;
+  for (int e = e_lo; e < e_hi; ++e) {
+    const bf16_t* ds_g = ds.p + ((long)(e - b0) * heads + head) * ds.plane
+        + qtile * BQ;
+    const bf16_t* k_g = k.base(e, head);
+    f32x4 dq_acc[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dq_acc[c] = f32x4{0, 0, 0, 0};
+
+#pragma unroll
+    for (int t = 0; t < NKV; ++t) {
+      char* dsl = lds[buf];
+      char* kl = lds[2 + buf];
+      buf ^= 1;
+      stage_store(dsreg, dsl);
+      stage_store(kreg, kl);
+      ds_sum_add(dsreg.v0, sum[t]);
+      ds_sum_add(dsreg.v1, sum[t] + 8);
+      // the buffer written here was last read two tiles ago, before the
+      // barrier of the previous tile
+      __syncthreads();
+      if (t + 1 < NKV) {
+        const int next_rows = min(BK, Lk - (t + 1) * BK);
+        stage_load_off(ds_g + (long)(t + 1) * BK * ds.pitch, ds_off,
+                       next_rows, col_ok[0], col_ok[1], dsreg);
+        stage_load_off(k_g + (long)(t + 1) * BK * k.rs, k_off, next_rows,
+                       true, true, kreg);
+      } else if (e + 1 < e_hi) {
+        stage_load_off(ds_g + (long)heads * ds.plane, ds_off, min(BK, Lk),
+                       col_ok[0], col_ok[1], dsreg);
+        stage_load_off(k.base(e + 1, head), k_off, min(BK, Lk), true, true,
+                       kreg);
+      }
+
+      bf16x8 ds_frag[2];
+#pragma unroll
+      for (int kblk = 0; kblk < 2; ++kblk)
+        ds_frag[kblk] = frag_tr(dsl, wave * 16, kblk);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        f32x4 acc = dq_acc[c];
+#pragma unroll
+        for (int kblk = 0; kblk < 2; ++kblk) {
+          bf16x8 kf = frag_tr(kl, c * 16, kblk);
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ds_frag[kblk], kf,
+                                                        acc, 0, 0, 0);
+        }
+        dq_acc[c] = acc;
+      }
+    }
+
+    bf16_t* dq_g = dq.base(e, head) + (long)qtile * BQ * dq.rs;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg) {
+      const int row = wave * 16 + (lane >> 4) * 4 + reg;
+      if (row < q_rows) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          dq_g[(long)row * dq.rs + c * 16 + (lane & 15)] =
+              (bf16_t)(dq_acc[c][reg] * scale);
+        }
+      }
+    }
+  }
+
+  float (*tile)[BK + 1] = reinterpret_cast<float (*)[BK + 1]>(&lds[0][0]);
+  const bool add = direct && accumulate && g * bias_repeat < b0;
+  float* out = sum_out + (long)blockIdx.z * chunk_stride
+      + ((long)((direct ? g : gl) * heads + head) * Lq + (long)qtile * BQ)
+          * Lk;
+  const int kvc = threadIdx.x & 63;
+#pragma unroll
+  for (int t = 0; t < NKV; ++t) {
+    __syncthreads();   // the tile's last readers: the MFMAs, or tile t - 1
+#pragma unroll
+    for (int pass = 0; pass < 2; ++pass) {
+      const int idx = threadIdx.x + pass * 256;
+      const int row = idx >> 3;
+      const int c8 = (idx & 7) << 3;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) tile[c8 + j][row] = sum[t][pass * 8 + j];
+    }
+    __syncthreads();
+    const int kv_rows = min(BK, Lk - t * BK);
+    for (int qq = threadIdx.x >> 6; qq < q_rows; qq += NWAVES) {
+      if (kvc < kv_rows) {
+        float* addr = out + (long)qq * Lk + t * BK + kvc;
+        const float val = tile[qq][kvc];
+        *addr = add ? *addr + val : val;
+      }
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // split backward (r02): the combined dK/dV kernel sits at 196-249 VGPRs
 // = 2 waves/SIMD.  Splitting recomputes S^T/P^T once more (5 -> 7
 // GEMM-equivalents) but the dV pass drops to ~4 waves/SIMD and the dK
@@ -2010,7 +2207,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  double dropout_p,
                                  c10::optional<at::Tensor> rng_state,
                                  c10::optional<int64_t> ds_scratch_bytes,
-                                 c10::optional<at::Tensor> delta_in) {
+                                 c10::optional<at::Tensor> delta_in,
+                                 c10::optional<int64_t> dq_entries_per_block) {
   check_qkv_bias(q, k, v, bias, bias_repeat, q_repeat, "attn_bwd");
   const bool has_drop = dropout_p != 0.0;
   BwdDrop<true> dr{};
@@ -2114,6 +2312,21 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
               ds_cap);
   const bool use_ds = need_dbias && ds_cap > 0 && !split_dkv;
 
+  // dBias out of the dQ-from-dS kernel (attn_bwd_dq_dbias_kernel):
+  // batch entries of a repeat group per block, None = what fills the
+  // device, 0 = the two kernels (dQ, then the sum), as
+  // AF2AMD_DQ_DBIAS_FUSED=0 selects everywhere.  Automatic takes the
+  // fused kernel up to four kv tiles (Lk <= 256, what was measured); an
+  // explicit count takes it up to six (Lk <= 384).  Longer Lk, and slices with more dbias elements
+  // than an int holds, stay on the two kernels.
+  static const bool dq_dbias_fused_env = [] {
+    const char* e = getenv("AF2AMD_DQ_DBIAS_FUSED");
+    return !(e != nullptr && e[0] == '0');
+  }();
+  const int64_t epb_arg = dq_entries_per_block.value_or(-1);
+  TORCH_CHECK(!dq_entries_per_block.has_value() || epb_arg >= 0,
+              "attn_bwd: dq_entries_per_block must be >= 0, got ", epb_arg);
+
   const int n_q = (Lq + BQ - 1) / BQ, n_k = (Lk + BK - 1) / BK;
   const long ds_plane = (long)n_q * BQ * n_k * BK;  // padded to whole tiles
   int ds_slice = 0;  // batch entries per slice
@@ -2209,6 +2422,29 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
     // next slice overwrites it.  Slices need not align to repeat groups:
     // the sum adds to groups an earlier slice started.
     const int R = (int)bias_repeat;
+    const long HLL = (long)H * Lq * Lk;   // dbias elements of one group
+    const long groups_cap = ((long)ds_slice + R - 1) / R + 1;
+    // the fused kernel's 32-bit row offsets inside a tile
+    const bool fused = groups_cap * HLL <= INT_MAX &&
+        (long)BK * n_q * BQ <= INT_MAX && kvv.rs > 0 &&
+        (long)BK * kvv.rs <= INT_MAX &&
+        (dq_entries_per_block.has_value()
+             ? epb_arg != 0 && n_k <= DQ_DBIAS_MAX_NKV
+             : dq_dbias_fused_env && n_k <= 4);
+#define DQ_DBIAS_FOR_NKV(DO)                                                  \
+  switch (n_k) {                                                              \
+    case 1: DO(1); break;                                                     \
+    case 2: DO(2); break;                                                     \
+    case 3: DO(3); break;                                                     \
+    case 4: DO(4); break;                                                     \
+    case 5: DO(5); break;                                                     \
+    default: DO(6); break;                                                    \
+  }
+    const void* fused_kernel = nullptr;
+#define DQ_DBIAS_PTR(NKV)                                                     \
+  fused_kernel = reinterpret_cast<const void*>(&attn_bwd_dq_dbias_kernel<NKV>)
+    DQ_DBIAS_FOR_NKV(DQ_DBIAS_PTR)
+#undef DQ_DBIAS_PTR
     for (int b0 = 0; b0 < B; b0 += ds_slice) {
       const int b1 = std::min(B, b0 + ds_slice);
       dsv = DsView{reinterpret_cast<bf16_t*>(ds_buf.data_ptr()), ds_plane,
@@ -2217,6 +2453,59 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
       if (has_mask) { DISPATCH_DKV(true, true, DBIAS_STORE); }
       else { DISPATCH_DKV(true, false, DBIAS_STORE); }
       check_launch("attn_bwd_dkv_kernel");
+      if (fused) {
+        const int g0 = b0 / R, g1 = (b1 - 1) / R;
+        const int ng = g1 - g0 + 1;
+        const int span = std::min(R, b1 - b0);  // most entries of a group
+        long epb = epb_arg;
+        if (epb <= 0) {
+          // as many chunks per group as keep the whole grid resident at
+          // once: every block then does the same share of the work
+          const long resident = colsum_grid(fused_kernel, 256,
+                                            COLSUM_MAX_BLOCKS);
+          const long chunks = std::max(1L, resident / ((long)n_q * ng * H));
+          epb = (span + chunks - 1) / chunks;
+        }
+        epb = std::min<long>(std::max(1L, epb), span);
+        const int nchunk = (int)((span + epb - 1) / epb);
+        TORCH_CHECK(nchunk <= 65535 && (long)ng * H <= 65535,
+                    "attn_bwd: dQ + dBias grid too large");
+        const bool direct = nchunk == 1;
+        const long C = (long)ng * HLL;
+        at::Tensor part;
+        float* sum_out = dbias.data_ptr<float>();
+        if (!direct) {
+          // every block stores its whole partial: no zero fill
+          part = at::empty({nchunk, C}, dbias.options());
+          sum_out = part.data_ptr<float>();
+        }
+#define LAUNCH_DQ_DBIAS(NKV)                                                  \
+  hipLaunchKernelGGL((attn_bwd_dq_dbias_kernel<NKV>),                         \
+                     dim3(n_q, ng * H, nchunk), dim3(256), 0, stream, dsv,    \
+                     kvv, dqv, sum_out, direct ? 0L : C, Lq, Lk, H,           \
+                     (float)scale, R, b0, b1, g0, (int)epb, direct ? 1 : 0,   \
+                     b0 > 0 ? 1 : 0)
+        DQ_DBIAS_FOR_NKV(LAUNCH_DQ_DBIAS)
+#undef LAUNCH_DQ_DBIAS
+        check_launch("attn_bwd_dq_dbias_kernel");
+        if (!direct) {
+          // chunks in order; the slice's first group is added to where
+          // an earlier slice started it
+          float* dst = dbias.data_ptr<float>() + (long)g0 * HLL;
+          const bool cont = b0 > 0 && (long)g0 * R < b0;
+          if (cont) {
+            colsum_fold_launch(sum_out, dst, nchunk, HLL, true, stream,
+                               false, C);
+            if (ng > 1)
+              colsum_fold_launch(sum_out + HLL, dst + HLL, nchunk, C - HLL,
+                                 false, stream, false, C);
+          } else {
+            colsum_fold_launch(sum_out, dst, nchunk, C, false, stream);
+          }
+          check_launch("colsum_fold (dbias)");
+        }
+        continue;
+      }
       hipLaunchKernelGGL(attn_bwd_dq_from_ds_kernel,
                          dim3(n_q, (b1 - b0) * H), dim3(256), 0, stream, dsv,
                          kvv, dqv, Lq, Lk, H, (float)scale);
@@ -2228,6 +2517,7 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                          b0, b1, g0, b0 > 0 ? 1 : 0);
       check_launch("attn_dbias_sum_kernel");
     }
+#undef DQ_DBIAS_FOR_NKV
     return {dq, dk, dv, dbias};
   }
 

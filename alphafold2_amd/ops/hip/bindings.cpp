@@ -72,6 +72,11 @@ std::vector<at::Tensor> egnn_core_bwd(
 long egnn_core_max_edge_dim();
 at::Tensor pairrep_fwd(at::Tensor left, at::Tensor right, at::Tensor emb,
                        at::Tensor rel);
+bool pairrep_bwd_covers(at::Tensor dy, long emb_rows);
+std::vector<at::Tensor> pairrep_bwd(at::Tensor dy, at::Tensor rel,
+                                    long emb_rows);
+at::Tensor colsum_fold(at::Tensor part,
+                       c10::optional<at::Tensor> accumulate_into, bool v1);
 std::vector<at::Tensor> attn_fwd(at::Tensor q, at::Tensor k, at::Tensor v,
                                  c10::optional<at::Tensor> bias,
                                  c10::optional<at::Tensor> mask,
@@ -92,7 +97,8 @@ std::vector<at::Tensor> attn_bwd(at::Tensor dout, at::Tensor q, at::Tensor k,
                                  double dropout_p,
                                  c10::optional<at::Tensor> rng_state,
                                  c10::optional<int64_t> ds_scratch_bytes,
-                                 c10::optional<at::Tensor> delta);
+                                 c10::optional<at::Tensor> delta,
+                                 c10::optional<int64_t> dq_entries_per_block);
 std::vector<at::Tensor> attn_gate_bwd(at::Tensor dy, at::Tensor out,
                                       at::Tensor g, at::Tensor dg_out,
                                       bool want_colsum);
@@ -144,6 +150,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fused pair-rep build: outer sum + rel-pos embedding gather "
         "(gfx950, K13)", py::arg("left"), py::arg("right"), py::arg("emb"),
         py::arg("rel"));
+  m.def("pairrep_bwd", &pairrep_bwd,
+        "pair-rep backward from one read of dy -> [dleft, dright, demb], "
+        "fp32 sums rounded once; no atomics (gfx950, K13)",
+        py::arg("dy"), py::arg("rel"), py::arg("emb_rows"));
+  m.def("pairrep_bwd_covers", &pairrep_bwd_covers,
+        "whether pairrep_bwd covers dy's shape, dtype and layout on the "
+        "current device",
+        py::arg("dy"), py::arg("emb_rows"));
+  m.def("colsum_fold", &colsum_fold,
+        "fixed-order fold of (nb, C) fp32 partial rows -> (C,), or added "
+        "into accumulate_into in place; v1 keeps the scalar body",
+        py::arg("part"), py::arg("accumulate_into") = c10::nullopt,
+        py::arg("v1") = false);
   m.def("ipa_core_fwd", &ipa_core_fwd,
         "fused fp32 IPA attention core forward -> [out, attn, gpts]; attn "
         "and gpts are saved for the backward only with save_stats "
@@ -242,7 +261,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("ds_scratch_bytes") = c10::nullopt,
         // rowsum(dO * O) as fp32 (B, h, Lq) when the caller already has it
         // (attn_gate_bwd): no attn_delta_kernel is launched
-        py::arg("delta") = c10::nullopt);
+        py::arg("delta") = c10::nullopt,
+        // for tests: batch entries per block of the fused dQ + dBias
+        // kernel (Lk <= 384); None = automatic (fused up to Lk = 256),
+        // 0 = the two kernels (dQ, then the sum)
+        py::arg("dq_entries_per_block") = c10::nullopt);
   m.def("attn_gate_bwd", &attn_gate_bwd,
         "gate backward of gated attention in one pass -> [dO, delta"
         "[, colsum]]; dg goes into dg_out, a slice of the packed gradient "

@@ -472,10 +472,8 @@ std::vector<at::Tensor> attn_gate_bwd(at::Tensor dy, at::Tensor out,
 
   std::vector<at::Tensor> ret = {d_o.permute({0, 2, 1, 3}), delta};
   if (want_colsum) {
-    hipLaunchKernelGGL(colsum_fold_kernel, dim3((C + 15) / 16),
-                       dim3(COLSUM_FOLD_THREADS), 0, stream,
-                       partials.data_ptr<float>(), colsum.data_ptr<float>(),
-                       (int)grid, (int)C);
+    colsum_fold_launch(partials.data_ptr<float>(), colsum.data_ptr<float>(),
+                       grid, C, false, stream);
     ret.push_back(colsum);
   }
   return ret;

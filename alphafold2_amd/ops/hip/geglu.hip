@@ -289,9 +289,7 @@ std::vector<at::Tensor> geglu_bwd_colsum(at::Tensor dy, at::Tensor x) {
                      reinterpret_cast<const T*>(x.data_ptr()),
                      reinterpret_cast<T*>(dx.data_ptr()), rows, H, row_shift,
                      partials.data_ptr<float>());
-  hipLaunchKernelGGL(colsum_fold_kernel, dim3((H2 + 15) / 16),
-                     dim3(COLSUM_FOLD_THREADS), 0, stream,
-                     partials.data_ptr<float>(), colsum.data_ptr<float>(),
-                     (int)grid, H2);
+  colsum_fold_launch(partials.data_ptr<float>(), colsum.data_ptr<float>(),
+                     grid, H2, false, stream);
   return {dx, colsum};
 }

@@ -454,11 +454,8 @@ std::vector<at::Tensor> wgrad_stream(const at::Tensor& dY,
   TORCH_CHECK(err == hipSuccess, "wgrad: launch failed: ",
               hipGetErrorString(err));
   if (slots > 1) {
-    hipLaunchKernelGGL(colsum_fold_kernel,
-                       dim3((unsigned int)((rowlen + 15) / 16)),
-                       dim3(COLSUM_FOLD_THREADS), 0, stream,
-                       part.data_ptr<float>(), out.data_ptr<float>(),
-                       (int)slots, (int)rowlen);
+    colsum_fold_launch(part.data_ptr<float>(), out.data_ptr<float>(), slots,
+                       rowlen, false, stream);
     err = hipGetLastError();
     TORCH_CHECK(err == hipSuccess, "wgrad: fold launch failed: ",
                 hipGetErrorString(err));

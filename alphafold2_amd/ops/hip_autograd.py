@@ -953,8 +953,8 @@ def hip_egnn_core(P, Q, x, edges, W_e, w_d, W2, b2, Wc1, bc1, Wc2, bc2, eps,
 class _PairRepFn(torch.autograd.Function):
     """Fused pair-rep build (K13): out[b,i,j] = left[i] + right[j] +
     emb[rel[i,j]].  Forward writes the (b,n,n,d) tensor ONCE (the eager
-    composition takes three full passes); backward is the standard
-    reduction trio (row/col sums + index_add on the embedding)."""
+    composition takes three full passes); backward is ext.pairrep_bwd: the
+    three sums from one read of dy, no atomics."""
 
     @staticmethod
     @custom_fwd(device_type='cuda', cast_inputs=torch.bfloat16)
@@ -969,13 +969,28 @@ class _PairRepFn(torch.autograd.Function):
     @custom_bwd(device_type='cuda')
     def backward(ctx, dy):
         (rel,) = ctx.saved_tensors
-        d = dy.shape[-1]
-        dleft = dy.sum(dim=2)
-        dright = dy.sum(dim=1)
-        demb = torch.zeros(ctx.emb_rows, d, device=dy.device,
-                           dtype=torch.float32)
-        demb.index_add_(0, rel.reshape(-1), dy.reshape(-1, d).float())
-        return dleft, dright, demb.to(dy.dtype), None
+        ext = _load_ext()
+        if not _PAIRREP_BWD_V1 and ext.pairrep_bwd_covers(dy, ctx.emb_rows):
+            dleft, dright, demb = ext.pairrep_bwd(dy, rel, ctx.emb_rows)
+            return dleft, dright, demb, None
+        return (*_pairrep_bwd_composed(dy, rel, ctx.emb_rows), None)
+
+
+# AF2AMD_PAIRREP_BWD_V1=1 keeps the library composition below
+_PAIRREP_BWD_V1 = _os.environ.get("AF2AMD_PAIRREP_BWD_V1", "0") == "1"
+
+
+def _pairrep_bwd_composed(dy, rel, emb_rows):
+    """Pair-rep backward from library ops: two wide sums and an fp32
+    index_add (global float atomics, so demb is not reproducible).  The
+    path of whatever ext.pairrep_bwd_covers turns down: a dy that is not
+    contiguous, d above 1024 or no multiple of 8, a table beyond LDS."""
+    d = dy.shape[-1]
+    dleft = dy.sum(dim=2)
+    dright = dy.sum(dim=1)
+    demb = torch.zeros(emb_rows, d, device=dy.device, dtype=torch.float32)
+    demb.index_add_(0, rel.reshape(-1), dy.reshape(-1, d).float())
+    return dleft, dright, demb.to(dy.dtype)
 
 
 def hip_pair_rep(left, right, emb, rel):

@@ -27,6 +27,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "pcgemm.hip"),
         os.path.join(HIP_DIR, "ffgemm.hip"),
         os.path.join(HIP_DIR, "wgrad.hip"),
+        os.path.join(HIP_DIR, "colsum.hip"),
         os.path.join(HIP_DIR, "pairrep.hip"),
         os.path.join(HIP_DIR, "ipacore.hip"),
         os.path.join(HIP_DIR, "se3core.hip"),
